@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: E-RAFT CorrBlock build + 12 lookups (one frame pair) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run does only what its headline figure needs: set up, W warmup steps (and the settle),
+the K timed steps, the outputs of the last timed step to DIR/<name>.npy if --dump-outputs is
+given, and the one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+Everything else described below (per-kernel timings and rooflines, the other build algorithms,
+the CPU baselines, the other BASELINE configs as `workloads`, the sharded leg of an N > 1 run)
+is measured only with --full.
 
 Workload (BASELINE.json metric "CorrBlock build+lookup frame-pairs/sec & HBM GB/s at DSEC
 480x640"): fmaps [1, 256, 60, 80] fp32 (DSEC 480x640 / 8), 4 levels, radius 4; one step =
@@ -14,7 +21,7 @@ data-path collective) -> weak scaling; value = frame pairs of ALL ranks / max-ov
 time.
 
 The step is replayed from one HIP graph so the timed loop is not host-launch-bound; after the
-W warmup steps, untimed replays continue for 0.25 s (settle()).  Separately, HIP events on the
+W warmup steps, untimed replays continue for 0.25 s (settle()).  With --full: HIP events on the
 launch stream bracket graphs of the build alone and of the 12 lookups alone, giving the build
 kernels' average durations (-> MFMA roofline) and the per-lookup average (-> HBM roofline).
 Rank 0 at N=1 also times the reference op sequence on the host CPU (oracle/torch_ops.py) on
@@ -96,10 +103,9 @@ WORKLOADS = {
 }
 CPU_SKIP = {"hires1280", "hires1920"}  # a CPU pair takes tens of seconds and >10 GB
 TRAIN_WORKLOADS = {"train"}
-# The default (DSEC) line also measures these BASELINE configs, one `workloads` entry each
-# (config 4 train, config 3 MVSEC B16, config 5's 1280x960 and 1920x1280 sizes on one GPU, config 2
-# the full E-RAFT forward),
-# so the driver's own run times them; --no-workloads skips them.
+# With --full the default (DSEC) line also measures these BASELINE configs, one `workloads` entry
+# each (config 4 train, config 3 MVSEC B16, config 5's 1280x960 and 1920x1280 sizes on one GPU,
+# config 2 the full E-RAFT forward); --no-workloads skips them.
 EXTRA_WORKLOADS = ("train", "mvsec", "hires1280", "hires1920", "e2e")
 ACHIEVABLE_HBM_GBS = 6290.0  # MI355X_MICROARCH.md: measured achievable HBM read bandwidth
 # The lookup's measured latency floor per workload: the same launch with neither the window
@@ -108,6 +114,31 @@ ACHIEVABLE_HBM_GBS = 6290.0  # MI355X_MICROARCH.md: measured achievable HBM read
 # profiles/r05t_kbench_lookup_ablations.txt; 1920x1280: profiles/r06za_kbench_lookup_1920.txt; median us).
 LOOKUP_NOLOAD_NOSTORE_US = {"dsec": 4.19, "mvsec": 11.49, "train": 6.86, "hires1280": 8.54, "hires1920": 14.78}
 LOOKUP_FLOOR_SOURCE = {"hires1920": "profiles/r06za_kbench_lookup_1920.txt"}
+# --dump-outputs: arrays above this many elements are written as a sample of this many (2 MiB of
+# float32 each; the largest dump, train, has 18 arrays: well under 64 MB in all)
+DUMP_MAX_ELEMS = 1 << 19
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy, float32 (float64 kept).
+    An array above DUMP_MAX_ELEMS elements is written as a 1-D sample of DUMP_MAX_ELEMS of its
+    flattened elements, at sorted indices drawn from a generator seeded by the array's name and
+    size alone: two runs (or two builds) with the same arguments sample the same elements."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), n])
+            idx = np.sort(rng.integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def parse():
@@ -119,7 +150,16 @@ def parse():
                     help="e2e: BASELINE config 2, the full E-RAFT forward (eraft_amd.model) at DSEC "
                          "480x640, warm start, 12 GRU iterations, random-init weights")
     ap.add_argument("--eager", action="store_true", help="launch eagerly instead of HIP graphs")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-kernel timings and rooflines, the other build "
+                         "algorithms, CPU baselines, the other BASELINE configs (`workloads`), and at N > 1 "
+                         "the sharded 1280x960 leg; the --no-* options below subtract from it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the lookups' "
+                         "outputs and the pyramid; train: the lookups and both fmap gradients; e2e: the flow "
+                         "predictions) to DIR/<name>.npy as float32, a fixed seeded sample of every array "
+                         f"above {DUMP_MAX_ELEMS} elements")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline sample budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sharded", action="store_true",
                     help="row-shard ONE frame pair's query rows over the ranks (SURVEY §8e): RCCL "
@@ -130,9 +170,10 @@ def parse():
                     help="--sharded: instead of chunks, double-buffer whole fmap2s across pairs "
                          "(pair k+1's broadcast during pair k; eager)")
     ap.add_argument("--no-sharded-leg", action="store_true",
-                    help="N > 1 dsec: skip the row-sharded 1280x960 leg reported beside the replica value")
+                    help="--full, N > 1 dsec: skip the row-sharded 1280x960 leg reported beside the replica value")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="N = 1 dsec: skip the train / mvsec / hires1280 / hires1920 / e2e entries of `workloads`")
+                    help="--full, N = 1 dsec: skip the train / mvsec / hires1280 / hires1920 / e2e entries of "
+                         "`workloads`")
     return ap.parse_args()
 
 
@@ -268,11 +309,16 @@ def run_e2e(args, world, rank, dev, role="primary"):
     im1, im2 = voxels(), voxels()
     finit = 2.0 * torch.randn(1, 2, H // 8, W // 8, device=dev, generator=g)
     launch = "eager"
+    keep = {}  # the last step's return value (in a graph: its static outputs), for --dump-outputs
+
+    def step():
+        keep.clear()  # the previous step's outputs are freed before this step allocates
+        keep["out"] = model(im1, im2, iters=iters, flow_init=finit)
+
     with torch.no_grad():
         for _ in range(args.warmup):
             model(im1, im2, iters=iters, flow_init=finit)
         torch.cuda.synchronize()
-        step = lambda: model(im1, im2, iters=iters, flow_init=finit)  # noqa: E731
         if not args.eager:
             # the whole forward (MIOpen convs, GRU elementwise ops, the HIP CorrBlock) as ONE
             # HIP graph: the GRU loop is otherwise bound by ~70 launches per iteration
@@ -306,6 +352,10 @@ def run_e2e(args, world, rank, dev, role="primary"):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and role == "primary" and rank == 0 and args.steps > 0:
+        flow_low, preds = keep["out"]  # the last timed step's (1/8-resolution flow, 12 predictions)
+        dump_outputs(args.dump_outputs, {"flow_low": flow_low,
+                                         **{f"flow_{i:02d}": p for i, p in enumerate(preds)}})
     res = {
         "metric": METRIC + " [config 2: full E-RAFT forward]",
         "value": round(args.steps * world / elapsed, 2), "unit": "frame-pairs/s", "n_gpus": world,
@@ -317,7 +367,7 @@ def run_e2e(args, world, rank, dev, role="primary"):
                    "global_batch": world, "launch": launch,
                    "parallelism": f"replicas x{world}"},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         budget = args.cpu_seconds * (0.5 if role == "workload" else 1.0)
         res["cpu_baseline"] = cpu_e2e(model, im1, im2, finit, iters, budget)
         res["speedup_vs_cpu"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
@@ -528,7 +578,7 @@ def main():
         run_e2e(args, world, rank, dev)
     else:
         res = run_corr(args, args.workload, args.sharded, world, rank, dev)
-        if world == 1 and not args.sharded and args.workload == "dsec" and not args.no_workloads:
+        if args.full and world == 1 and not args.sharded and args.workload == "dsec" and not args.no_workloads:
             # BASELINE configs 2, 3, 4 and 5 measured in the same (driver) run, beside `value`
             res["workloads"] = {}
             for wl in EXTRA_WORKLOADS:
@@ -545,7 +595,7 @@ def main():
                     ent = {"error": f"{type(exc).__name__}: {exc}"}
                 ent["wall_s"] = round(time.perf_counter() - t_w, 2)
                 res["workloads"][wl] = ent
-        if world > 1 and not args.sharded and args.workload == "dsec" and not args.no_sharded_leg:
+        if args.full and world > 1 and not args.sharded and args.workload == "dsec" and not args.no_sharded_leg:
             # the north_star's scaling case beside the replica value: ONE 1280x960 pair row-sharded
             # over the N ranks (chunked RCCL broadcast of fmap2, graph-captured), strong scaling
             try:
@@ -564,8 +614,9 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
     """One CorrBlock workload: returns the result dict on rank 0 (None elsewhere).  role "leg"
     (the sharded leg of an N > 1 run): no alternative builds, no CPU baseline; "workload" (an
     entry of the DSEC line's `workloads`): no alternative builds, CPU baselines on half the
-    sample budget."""
+    sample budget.  Without --full only the step is set up, warmed up and timed."""
     primary = role == "primary"
+    full = args.full
     from eraft_amd import CorrBlock, _lib
     from eraft_amd.corr import _alloc_grad_pyramid, _alloc_pyramid
 
@@ -599,7 +650,7 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
 
     algo = _lib.default_algo()
     ws = _lib.build_workspace(f1, f2, algo)  # the split operands (BF16X6 / F16X3), reused every step
-    ws_x3 = _lib.build_workspace(f1, f2, _lib.BUILD_F16X3)
+    ws_x3 = _lib.build_workspace(f1, f2, _lib.BUILD_F16X3) if full else None  # build_f16x3's
 
     def build_only():
         _lib.build(f1, f2, pyr, algo, ws)
@@ -624,16 +675,26 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
         for c in coords:       # hands the freed previous iteration's output to the next lookup
             _lib.lookup(pyr, c, r, outs[0], H, W)
 
+    # --dump-outputs: the step leaves its block and its LAST lookup's output here (in a HIP graph:
+    # the graph's static memory, rewritten by every replay).  The earlier lookups' outputs are not
+    # held: each is freed before the next is allocated, as in the model's loop, which the timing
+    # depends on (one reused output buffer, see library_calls_12_outputs); the dump recomputes them.
+    keep = {}
+
     def api_pair():  # the drop-in CorrBlock: ctor (pyramid + workspace) and 12 __call__s
         cb = CorrBlock(f1, f2, num_levels=L, radius=r)
+        out = None
         for c in coords:
-            cb(c)
+            del out  # free the previous output first: the next lookup gets the same buffer
+            out = cb(c)
+        keep["block"], keep["last"] = cb, out
 
     if train:
         # backward of the 12 lookups + pyramid + product (eraft.py:128 detaches coords)
         gouts = [torch.randn(B, L * K, H, W, device=dev, generator=g) for _ in range(iters)]
-        gpyr = _alloc_grad_pyramid(B, H, W, L, f1, zero=True)
-        gbuf = gpyr[0]._base  # the one allocation behind every level view
+        if full:  # the backward kernels timed alone
+            gpyr = _alloc_grad_pyramid(B, H, W, L, f1, zero=True)
+            gbuf = gpyr[0]._base  # the one allocation behind every level view
         f1g = f1.clone().requires_grad_(True)
         f2g = f2.clone().requires_grad_(True)
 
@@ -651,9 +712,11 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
             return _lib.build_bwd(gpyr[0], f1, f2)
 
         def autograd_step():  # what training runs: CorrBlock forward + loss.backward() to both fmaps
+            keep.clear()  # the previous step's outputs and gradients are freed before this step allocates
             cb = CorrBlock(f1g, f2g, num_levels=L, radius=r)
             outs_ = [cb(c) for c in coords]
             torch.autograd.backward(outs_, gouts)
+            keep["outs"], keep["grads"] = [o.detach() for o in outs_], (f1g.grad, f2g.grad)  # --dump-outputs
             f1g.grad = None
             f2g.grad = None
 
@@ -680,6 +743,7 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
                 pipe["pending"] = dbuf.prefetch(f2 if rank == 0 else None)  # prologue: pair 0's fmap2
 
         def pair():
+            keep.clear()  # the previous step's block is freed before this step allocates
             if prefetch:
                 cur = pipe["pending"]
                 with torch.no_grad():
@@ -687,11 +751,13 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
                 blk = RowShardedCorrBlock(f1, cur, num_levels=L, radius=r, fmap1_is_slab=True)
                 for c in coords:
                     blk(c)
+                keep["block"] = blk
             elif sharded and world > 1:
                 # chunked broadcast: chunk k+1 arrives while chunk k's pyramid rows are built
                 blk = RowShardedCorrBlock(f1, f2, num_levels=L, radius=r, fmap1_is_slab=True, chunks=args.chunks)
                 for c in coords:
                     blk(c)
+                keep["block"] = blk
             elif sharded:  # one rank: the row-slab library calls over all rows
                 build_only()
                 run_lookups_reused()
@@ -763,11 +829,34 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
         if world > 1:
             dist.barrier()
 
+        if args.dump_outputs and primary and rank == 0:
+            # what the last timed step computed, as its caller receives it (sharded: rank 0's rows)
+            arrays = {}
+            if train:
+                arrays.update({f"lookup_{i:02d}": o for i, o in enumerate(keep["outs"])})
+                arrays["dfmap1"], arrays["dfmap2"] = keep["grads"]
+            else:
+                blk = keep.get("block")  # None: the one-rank row-slab library calls on pyr / outs[0]
+                for i, c in enumerate(coords[:-1]):  # recomputed from the last step's pyramid
+                    if blk is not None:
+                        arrays[f"lookup_{i:02d}"] = blk(c)
+                    else:
+                        arrays[f"lookup_{i:02d}"] = torch.empty_like(outs[0])
+                        _lib.lookup(pyr, c, r, arrays[f"lookup_{i:02d}"], H, W)
+                if "last" not in keep:  # the sharded steps return the last output into no variable
+                    keep["last"] = blk(coords[-1]) if blk is not None else outs[0]
+                arrays[f"lookup_{iters - 1:02d}"] = keep["last"]
+                if not sharded:
+                    arrays.update({f"pyramid_{l}": p for l, p in enumerate(blk.corr_pyramid)})
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, arrays)
+            del arrays
+
         # the same step with the other build algorithms, and through the public drop-in API
         # (CorrBlock ctor: pyramid + workspace allocation, then 12 __call__s), reported beside
-        # `value` — same K steps after W warmups, HIP graphs unless --eager
+        # `value` — same K steps after W warmups, HIP graphs unless --eager (--full)
         alt_values = {}
-        if primary and not train and not sharded:
+        if full and primary and not train and not sharded:
             def timed(fn):
                 st = fn
                 if launch == "hipgraph":
@@ -791,21 +880,23 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
             alt_values[f"library_calls_{BUILD_ALGO[algo]}"] = timed(lambda: (build_only(), run_lookups_reused()))
             alt_values[f"library_calls_12_outputs_{BUILD_ALGO[algo]}"] = timed(lambda: (build_only(), run_lookups()))
 
-        # per-kernel durations on the launch stream (graph_time_ms)
-        build_call_ms = graph_time_ms(build_only, stream)
-        if algo != _lib.BUILD_FP32:  # per-kernel: pack + MFMA, each timed alone (kernel-trace comparable)
-            pack_ms, mfma_ms = graph_time_ms(build_pack, stream), graph_time_ms(build_mfma, stream)
-            build_ms = pack_ms + mfma_ms
-        else:
-            pack_ms = mfma_ms = None
-            build_ms = build_call_ms
-        look_ms = graph_time_ms(run_lookups, stream) / iters
-        fp32_ms = graph_time_ms(build_fp32, stream, rep=4) if primary and algo != _lib.BUILD_FP32 else None
-        x3_ms = graph_time_ms(build_f16x3, stream, rep=4) if primary and algo == _lib.BUILD_BF16X6 else None
-        bwd_ms = graph_time_ms(run_bwd_kernels, stream, rep=4) if train else None
-        bwd_staged_ms = graph_time_ms(run_bwd_staged, stream, rep=4) if train else None
-        bwd_x3_ms = graph_time_ms(run_bwd_f16x3, stream, rep=4) if train and algo == _lib.BUILD_BF16X6 else None
-        if sharded and world > 1:  # per-rank broadcast time (eager, events on the stream)
+        # per-kernel durations on the launch stream (graph_time_ms): runs of their own, --full
+        pack_ms = mfma_ms = None
+        if full:
+            build_call_ms = graph_time_ms(build_only, stream)
+            if algo != _lib.BUILD_FP32:  # per-kernel: pack + MFMA, each timed alone (kernel-trace comparable)
+                pack_ms, mfma_ms = graph_time_ms(build_pack, stream), graph_time_ms(build_mfma, stream)
+                build_ms = pack_ms + mfma_ms
+            else:
+                build_ms = build_call_ms
+            look_ms = graph_time_ms(run_lookups, stream) / iters
+        fp32_ms = graph_time_ms(build_fp32, stream, rep=4) if full and primary and algo != _lib.BUILD_FP32 else None
+        x3_ms = graph_time_ms(build_f16x3, stream, rep=4) if full and primary and algo == _lib.BUILD_BF16X6 else None
+        bwd_ms = graph_time_ms(run_bwd_kernels, stream, rep=4) if full and train else None
+        bwd_staged_ms = graph_time_ms(run_bwd_staged, stream, rep=4) if full and train else None
+        bwd_x3_ms = (graph_time_ms(run_bwd_f16x3, stream, rep=4)
+                     if full and train and algo == _lib.BUILD_BF16X6 else None)
+        if full and sharded and world > 1:  # per-rank broadcast time (eager, events on the stream)
             ts = []
             for _ in range(5):
                 a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -839,8 +930,9 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
         lb *= frac_rows
         lvn = sum((H >> l) * (W >> l) for l in range(L))
         bb = B * D * (h1 - h0 + H) * W * 4 + B * (h1 - h0) * W * lvn * 4
-    look_gbs = lb / (look_ms * 1e-3) / 1e9
-    hbm_gbs = (bb + iters * lb) / (build_ms + iters * look_ms) / 1e6
+    if full:
+        look_gbs = lb / (look_ms * 1e-3) / 1e9
+        hbm_gbs = (bb + iters * lb) / (build_ms + iters * look_ms) / 1e6
 
     if rank == 0:
         res = {
@@ -867,21 +959,24 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
                                       f"replicas x{world} (independent frame pairs per GPU)"},
             "build_algo": BUILD_ALGO[algo],
             "build_arith": BUILD_ARITH[algo],
-            "roofline": build_roofline(algo, fl, bb, build_ms, build_traffic(wl_name, algo)),
-            "roofline_lookup": {"bound": "hbm", "kernel": "lookup_kernel",
-                                "achieved": round(look_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                "frac": round(look_gbs / PEAK_HBM_GBS, 4),
-                                "traffic": traffic(wl_name, "lookup_kernel"),
-                                "avg_us": round(look_ms * 1e3, 3), "bytes_per_launch": lb,
-                                "ceiling": lookup_ceiling(wl_name, lb, look_ms, traffic(wl_name, "lookup_kernel"))},
-            "kernel_timing": "HIP events around 10 back-to-back launches of one kernel in one HIP graph on "
-                             "the launch stream, median of 5: the gaps between dependent launches of DIFFERENT "
-                             "kernels are not in avg_us (the build's pack -> MFMA boundary is in "
-                             "kernel_us.build_call_in_graph); within one run this agrees with rocprofv3's "
-                             "kernel trace (profiles/r05l_dsec_kernel_stats.csv vs prof run: MFMA 70.3 vs "
-                             "69.2 us median, lookup 5.80 vs 5.59), across boxes it varies by up to 8 %",
-            "hbm_gbs_algorithmic": round(hbm_gbs, 1),
         }
+        if full:
+            res["roofline"] = build_roofline(algo, fl, bb, build_ms, build_traffic(wl_name, algo))
+            res["roofline_lookup"] = {
+                "bound": "hbm", "kernel": "lookup_kernel",
+                "achieved": round(look_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                "frac": round(look_gbs / PEAK_HBM_GBS, 4),
+                "traffic": traffic(wl_name, "lookup_kernel"),
+                "avg_us": round(look_ms * 1e3, 3), "bytes_per_launch": lb,
+                "ceiling": lookup_ceiling(wl_name, lb, look_ms, traffic(wl_name, "lookup_kernel"))}
+            res["kernel_timing"] = (
+                "HIP events around 10 back-to-back launches of one kernel in one HIP graph on "
+                "the launch stream, median of 5: the gaps between dependent launches of DIFFERENT "
+                "kernels are not in avg_us (the build's pack -> MFMA boundary is in "
+                "kernel_us.build_call_in_graph); within one run this agrees with rocprofv3's "
+                "kernel trace (profiles/r05l_dsec_kernel_stats.csv vs prof run: MFMA 70.3 vs "
+                "69.2 us median, lookup 5.80 vs 5.59), from one machine to another it varies by up to 8 %")
+            res["hbm_gbs_algorithmic"] = round(hbm_gbs, 1)
         if pack_ms is not None:
             res["roofline"]["kernel_us"] = {PACK_KERNEL[algo]: round(pack_ms * 1e3, 2),
                                             MFMA_KERNEL[algo]: round(mfma_ms * 1e3, 2),
@@ -900,7 +995,7 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
                                       "than fp32); library_calls_*: the default build through the C-ABI calls "
                                       "with one reused output buffer, and with 12 distinct preallocated outputs "
                                       "(round 3's step: at B16 their 394 MB stream past the MALL)")
-        if train:
+        if full and train:
             res["backward_kernels"] = {
                 "phase": f"corr_backward: {iters} lookup backwards in one launch + pool fold into dC + 2 "
                          f"{BUILD_ALGO[_lib.backward_algo(algo)]} split GEMMs (dF1 = dC F2^T, dF2 = F1^T dC, "
@@ -928,7 +1023,7 @@ def run_corr(args, wl_name, sharded, world, rank, dev, role="primary"):
                 "backend": os.environ.get("ERAFT_AMD_DIST_BACKEND", "nccl")}
         if capture_error is not None:
             res["capture_error"] = capture_error
-        if role != "leg" and world == 1 and not args.no_cpu_baseline and wl_name not in CPU_SKIP:
+        if full and role != "leg" and world == 1 and not args.no_cpu_baseline and wl_name not in CPU_SKIP:
             budget = args.cpu_seconds * (1.0 if primary else 0.5)
             cb = cpu_baseline(wl, budget, train)
             res["cpu_baseline"] = cb

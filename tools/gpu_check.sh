@@ -3,6 +3,7 @@
 #   tools/gpu_check.sh <tag> [bench args...]
 set -o pipefail
 TAG=${1:-run}; shift || true
+set -- --full "$@"  # bench.py: every field of the line (rooflines, workloads, CPU baselines), not only the headline
 mkdir -p gpurun_out
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > gpurun_out/gpu_tests_$TAG.log 2>&1 || { echo "TESTS FAILED"; tail -30 gpurun_out/gpu_tests_$TAG.log; exit 3; }
 tail -3 gpurun_out/gpu_tests_$TAG.log

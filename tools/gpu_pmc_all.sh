@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 for w in train mvsec mvsec_crop hires1280 hires1920; do
   OUT=gpurun_out/prof_${TAG}_$w
   mkdir -p "$OUT"
-  ARGS="--workload $w --no-cpu-baseline --steps 20 --warmup 5"
+  ARGS="--workload $w --full --no-cpu-baseline --steps 20 --warmup 5"
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- python3 bench.py $ARGS > "$OUT/bench_trace.json" 2> "$OUT/trace.err"
   timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc2" -o run --output-format csv -- python3 bench.py $ARGS > /dev/null 2> "$OUT/pmc2.err"
   timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc3" -o run --output-format csv -- python3 bench.py $ARGS > /dev/null 2> "$OUT/pmc3.err"

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 # PROG=tools/time_conv_bwd.py tools/profile.sh <tag> [args]: profile another script instead
 PROG=${PROG:-bench.py}
-if [ "$PROG" = bench.py ]; then ARGS="--no-cpu-baseline --steps 50 --warmup 10 $*"; else ARGS="$*"; fi
+if [ "$PROG" = bench.py ]; then ARGS="--full --no-cpu-baseline --steps 50 --warmup 10 $*"; else ARGS="$*"; fi
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- python3 $PROG $ARGS > "$OUT/bench_trace.json" 2> "$OUT/trace.err"
 # PMC in separate passes (never combined with --sys-trace / runtime traces)
 P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS"
