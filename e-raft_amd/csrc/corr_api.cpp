@@ -81,6 +81,17 @@ static int check_radius(const char *fn, int radius) {
     return CORR_OK;
 }
 
+// Sizes the on-demand calls share: check_dims plus D and the operands' total size.
+static int check_ondemand(const char *fn, int B, int D, int H, int W, int levels) {
+    int rc = check_dims(fn, B, 1, H, W, levels);
+    if (rc) return rc;
+    if (D < 1) return fail(CORR_EINVAL, "%s: D must be >= 1 (got %d)", fn, D);
+    // the launch grids are sized for feature maps of up to 2^37 (padded) floats each
+    if (D > (1 << 20) || (long double)B * H * W * ((D + 3) & ~3) > (long double)(1LL << 37))
+        return fail(CORR_EINVAL, "%s: B*H*W*D too large", fn);
+    return CORR_OK;
+}
+
 }  // namespace corr
 
 using namespace corr;
@@ -378,6 +389,40 @@ int corr_backward(int algo, const float *const *coords_rows, const float *const 
     return hip_status(launch_backward(algo, coords_rows, grad_out_rows, T, fmap1_rows, NQ, fmap2, B, D, H, W, levels,
                                       radius, lp, dfmap1_rows, dfmap2, workspace, (hipStream_t)stream),
                       fn);
+}
+
+size_t corr_ondemand_workspace(int B, int D, int H, int W, int levels) {
+    if (check_ondemand("corr_ondemand_workspace", B, D, H, W, levels)) return 0;
+    return ondemand_workspace_bytes(B, D, H, W, levels);
+}
+
+int corr_ondemand_prepare(const float *fmap1, const float *fmap2, int B, int D, int H, int W, int levels,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+    static const char *fn = "corr_ondemand_prepare";
+    g_err[0] = 0;
+    int rc = check_ondemand(fn, B, D, H, W, levels);
+    if (rc) return rc;
+    if ((rc = check_ptr(fn, fmap1, "fmap1")) || (rc = check_ptr(fn, fmap2, "fmap2"))) return rc;
+    if (!workspace) return fail(CORR_EINVAL, "%s: workspace is NULL", fn);
+    if ((uintptr_t)workspace % 16) return fail(CORR_EINVAL, "%s: workspace is not 16-byte aligned", fn);
+    const size_t need = ondemand_workspace_bytes(B, D, H, W, levels);
+    if (workspace_bytes < need)
+        return fail(CORR_EINVAL, "%s: workspace of %zu bytes needed, got %zu", fn, need, workspace_bytes);
+    return hip_status(launch_ondemand_prepare(fmap1, fmap2, B, D, H, W, levels, workspace, (hipStream_t)stream), fn);
+}
+
+int corr_ondemand_lookup(const void *workspace, const float *coords, int B, int D, int H, int W, int levels,
+                         int radius, int flags, float *out, void *stream) {
+    static const char *fn = "corr_ondemand_lookup";
+    g_err[0] = 0;
+    int rc = check_ondemand(fn, B, D, H, W, levels);
+    if (rc || (rc = check_radius(fn, radius))) return rc;
+    if (flags & ~CORR_ONDEMAND_GENERAL) return fail(CORR_EINVAL, "%s: unknown flags 0x%x", fn, flags);
+    if (!workspace) return fail(CORR_EINVAL, "%s: workspace is NULL", fn);
+    if ((uintptr_t)workspace % 16) return fail(CORR_EINVAL, "%s: workspace is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, coords, "coords")) || (rc = check_ptr(fn, out, "out"))) return rc;
+    return hip_status(
+        launch_ondemand_lookup(workspace, coords, B, D, H, W, levels, radius, flags, out, (hipStream_t)stream), fn);
 }
 
 size_t corr_lookup_conv_weights_bytes(void) { return lookup_conv_weights_bytes(); }

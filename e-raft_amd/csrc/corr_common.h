@@ -170,6 +170,12 @@ hipError_t launch_pyramid_export(const ConstLevelPtrs &pyr, long BN, int H, int 
                                  hipStream_t s);
 hipError_t launch_pyramid_import(const ConstLevelPtrs &src, long BN, int H, int W, int levels, const LevelPtrs &pyr,
                                  hipStream_t s);
+// On-demand lookup (corr_ondemand.hip): pixel-major operands in `ws`, no pyramid.
+size_t ondemand_workspace_bytes(int B, int D, int H, int W, int levels);
+hipError_t launch_ondemand_prepare(const float *f1, const float *f2, int B, int D, int H, int W, int levels, void *ws,
+                                   hipStream_t s);
+hipError_t launch_ondemand_lookup(const void *ws, const float *coords, int B, int D, int H, int W, int levels,
+                                  int radius, int flags, float *out, hipStream_t s);
 size_t build_bwd_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bwd(const float *grad_c, const float *f1, int NQ, const float *f2, int B,
                             int D, int H, int W, float *df1, float *df2, float *ws, hipStream_t s);

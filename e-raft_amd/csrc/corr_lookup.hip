@@ -42,6 +42,7 @@
 #include "corr_build_common.h"
 #include "corr_common.h"
 #include "corr_div.h"
+#include "corr_taps.h"
 
 namespace corr {
 namespace {
@@ -50,41 +51,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Sentinel anchor for NaN / huge coordinates: every window cell is outside the map.
-constexpr int kFarAnchor = -(1 << 28);
-
-struct Axis {
-    float f;   // floor(ix) as float (may be NaN / huge)
-    float lo;  // (f + 1) - ix  : weight of corner f
-    float hi;  // ix - f        : weight of corner f + 1
-};
-
-// rden = recip_rn(size - 1), hoisted by the callers (per level)
-__device__ __forceinline__ Axis tap_axis(float c, float inv_scale, int t, int r, int size, float rden) {
-    // corr.py:41  centroid = coords / 2**l   (exact: power-of-two scale)
-    // corr.py:43  + delta (integer offsets from linspace(-r, r, 2r+1))
-    // utils.py:11 2*x/(W-1) - 1 ; grid_sample unnormalise ((x'+1)/2)*(W-1)
-    // The division is correctly rounded (corr_div.h: the same bits as __fdiv_rn in 3 VALU)
-    const float cl = c * inv_scale;
-    const float X = cl + (float)(t - r);
-    const float den = (float)(size - 1);
-    const float xn = __fsub_rn(div_rn(2.0f * X, den, rden), 1.0f);
-    const float ix = __fmul_rn(__fmul_rn(__fadd_rn(xn, 1.0f), 0.5f), den);
-    Axis a;
-    a.f = floorf(ix);
-    a.hi = __fsub_rn(ix, a.f);
-    a.lo = __fsub_rn(__fadd_rn(a.f, 1.0f), ix);
-    return a;
-}
-
-__device__ __forceinline__ int anchor_of(float f) {
-    return (f >= -1048576.0f && f <= 1048576.0f) ? (int)f : kFarAnchor;
-}
-
-__device__ __forceinline__ bool in_map(float xf, float yf, int Wl, int Hl) {
-    return xf >= 0.0f && xf < (float)Wl && yf >= 0.0f && yf < (float)Hl;
-}
 
 // True when every in-map corner of the query's taps lies inside its (S+2)^2 neighbourhood.
 template <int S>

@@ -31,7 +31,7 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_voxel_grid_tbilinear", "corr_lookup_bwd_multi", "corr_pool_fold", "corr_backward_workspace",
            "corr_backward", "corr_convex_upsample_bwd_workspace", "corr_convex_upsample_bwd", "corr_build_region",
            "corr_lookup_conv_bwd_workspace", "corr_lookup_conv_bwd", "corr_map_floats", "corr_pyramid_export",
-           "corr_pyramid_import")
+           "corr_pyramid_import", "corr_ondemand_workspace", "corr_ondemand_prepare", "corr_ondemand_lookup")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -135,7 +135,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_lookup_conv_bwd_workspace.argtypes = [i, i, i, i]
     lib.corr_lookup_conv_bwd_workspace.restype = sz
     lib.corr_lookup_conv_bwd.argtypes = [vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, sz, vp]
-    for f in ("corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
+    lib.corr_ondemand_workspace.argtypes = [i, i, i, i, i]
+    lib.corr_ondemand_workspace.restype = sz
+    lib.corr_ondemand_prepare.argtypes = [vp, vp, i, i, i, i, i, vp, sz, vp]
+    lib.corr_ondemand_lookup.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp]
+    for f in ("corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
@@ -535,3 +539,38 @@ def lookup_conv_bwd(levels, coords, radius, packed, out, relu, grad_out, grad_we
                                         int(bool(relu)), g, opt(grad_weight, "grad_weight"),
                                         opt(grad_bias, "grad_bias"), opt(grad_lookup, "grad_lookup"),
                                         None if ws is None else ws.data_ptr(), nbytes, _stream(coords)))
+
+
+ONDEMAND_GENERAL = 1  # corr_ondemand_lookup flag: the general path for every workgroup
+
+
+def ondemand_workspace(B, D, H, W, levels, device):
+    """A device workspace for corr_ondemand_prepare / _lookup (the pixel-major operands)."""
+    n = load().corr_ondemand_workspace(B, D, H, W, levels)
+    if n == 0:
+        raise CorrError(CORR_EINVAL, f"corr_ondemand_workspace: unsupported sizes B={B} D={D} {H}x{W}, {levels} levels")
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def ondemand_prepare(fmap1, fmap2, levels, workspace):
+    """corr_ondemand_prepare: fmap1 / fmap2 [B, D, H, W] -> the workspace's pixel-major rows of
+    fmap1 and of fmap2 pooled 0 .. levels-1 times."""
+    B, D, H, W = fmap2.shape
+    a, b, ws = _dev(fmap1, "fmap1"), _dev(fmap2, "fmap2"), _dev(workspace, "workspace")
+    with torch.cuda.device(fmap1.device):
+        _check(load().corr_ondemand_prepare(a, b, B, D, H, W, levels, ws, workspace.numel() * 4, _stream(fmap1)))
+
+
+def ondemand_lookup(workspace, coords, D, levels, radius, out, flags=0):
+    """corr_ondemand_lookup: coords [B, 2, H, W] -> out [B, levels*K, H, W] from a prepared
+    workspace of the same B, D, H, W, levels."""
+    B, _, H, W = coords.shape
+    ws, c, o = _dev(workspace, "workspace"), _dev(coords, "coords"), _dev(out, "out")
+    lib = load()
+    if workspace.numel() * 4 < lib.corr_ondemand_workspace(B, D, H, W, levels):
+        raise ValueError("workspace is smaller than corr_ondemand_workspace for these sizes")
+    K = (2 * radius + 1) ** 2
+    if out.numel() != B * levels * K * H * W:
+        raise ValueError(f"out has {out.numel()} floats, the lookup writes {B}x{levels * K}x{H * W}")
+    with torch.cuda.device(coords.device):
+        _check(lib.corr_ondemand_lookup(ws, c, B, D, H, W, levels, radius, flags, o, _stream(coords)))

@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .corr import CorrBlock
+from .ondemand import OnDemandCorrBlock
 from .utils import coords_grid
 
 
@@ -223,6 +224,12 @@ class ERAFT(nn.Module):
         self.subtype = config["subtype"].lower()
         if self.subtype not in ("standard", "warm_start"):
             raise ValueError(f"unknown subtype {self.subtype}")
+        # RAFT's switch: lookups computed from the feature maps (OnDemandCorrBlock; no all-pairs
+        # volume, inference only) instead of CorrBlock.  Config key, default off;
+        # ERAFT_AMD_ONDEMAND=1 / =0 overrides it.
+        alt = bool(config.get("alternate_corr", False)) if hasattr(config, "get") else False
+        env = os.environ.get("ERAFT_AMD_ONDEMAND")
+        self.alternate_corr = alt if env is None else env == "1"
         self.image_padder = ImagePadder(min_size=32)
         hdim, cdim = self.hidden_dim, self.context_dim
         self.fnet = BasicEncoder(output_dim=256, norm_fn="instance", dropout=0,
@@ -254,8 +261,8 @@ class ERAFT(nn.Module):
         image1 = self.image_padder.pad(image1).contiguous()
         image2 = self.image_padder.pad(image2).contiguous()
         fmap1, fmap2 = self.fnet([image1, image2])
-        corr_fn = CorrBlock(fmap1.float(), fmap2.float(), num_levels=self.corr_levels,
-                            radius=self.corr_radius)
+        block = OnDemandCorrBlock if self.alternate_corr else CorrBlock
+        corr_fn = block(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius)
         net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)
         n, _, h, w = image1.shape

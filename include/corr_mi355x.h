@@ -63,7 +63,9 @@ extern "C" {
  *        of the staged path, not bitwise); CORR_BACKWARD_EXACT_FOLD restores the bit-exact replay.
  *   202: the CORR_BUILD_BF16X6 backward GEMMs (corr_build_bwd_ex, corr_backward) give the fp32
  *        reference's results for non-finite inputs (+-inf where fp32 has +-inf; NaN only where it
- *        has NaN) instead of NaN for every output an infinity reaches. */
+ *        has NaN) instead of NaN for every output an infinity reaches.
+ *        Added under 202 (purely additive, no version change): corr_ondemand_workspace,
+ *        corr_ondemand_prepare, corr_ondemand_lookup. */
 int corr_version(void);
 
 /* Thread-local description of the last error on this thread ("" if none). */
@@ -284,6 +286,56 @@ int corr_backward(int algo, const float *const *coords_rows, const float *const 
                   const float *fmap1_rows, int NQ, const float *fmap2, int B, int D, int H, int W, int levels,
                   int radius, float *const *grad_pyr, float *dfmap1_rows, float *dfmap2, void *workspace,
                   size_t workspace_bytes, void *stream);
+
+/*
+ * On-demand window lookup: corr_lookup's output without the all-pairs pyramid (RAFT's
+ * AlternateCorrBlock; the reference keeps its import commented out, model/corr.py:5-9).  Average
+ * pooling is linear, so level l of the pyramid is the correlation of fmap1 with fmap2 pooled l
+ * times, and only the entries a lookup touches are computed, straight from the feature maps:
+ *   P_0 = fmap2,  P_l = avg_pool2d(P_{l-1}, 2, stride 2)            (fp32, corr_build's pool order)
+ *   C_l[b][n](y, x) = (sum_d fmap1[b][d][n] * P_l[b][d][y][x]) / sqrt(float(D))   inside H_l x W_l, else 0
+ *   out[b][l*K + i*(2r+1) + j][n] = bilinear(C_l[b][n], tap (i, j))
+ * Tap coordinates, floors, corner weights, zero padding, the corner order (nw, ne, sw, se, fmaf)
+ * and the channel order are corr_lookup's, bit for bit; out-of-map, far, NaN and +-inf coordinates
+ * and one-cell levels give exactly corr_lookup's zeros and NaNs.
+ *
+ * Accuracy: fp32 operands, fp32 fmaf accumulation (nothing is rounded to a narrower format); the
+ * dot products are summed in another order than the builds', so the output equals corr_lookup's
+ * on a corr_build pyramid within 1e-4 norm-relative (measured ~1e-6), not bit for bit.  Non-finite
+ * FEATURE values are not parity-checked: inf * 0 lands in other cells when features are pooled
+ * first.  Deterministic: no atomics, a fixed summation order.
+ *
+ * corr_ondemand_prepare pools fmap2 and writes both operands pixel-major into the workspace
+ * (16-byte aligned, >= corr_ondemand_workspace bytes), Dp = D rounded up to a multiple of 4:
+ *   float fmap1_rows[B][H*W][Dp]; then for l = 0 .. levels-1: float P_l[B][H_l*W_l][Dp]
+ * (channels D .. Dp-1 zero), so one cell's features are one contiguous row (1 KiB at D = 256):
+ * 4*B*Dp*(H*W + sum_l H_l*W_l) bytes, e.g. 92 MB at 160x240, D = 256, 4 levels, where the pyramid
+ * takes 7.9 GB.  corr_ondemand_lookup may then be called any number of times (every GRU
+ * iteration) with the same sizes.  corr_ondemand_workspace returns 0 for sizes the calls reject
+ * (B, D, H, W < 1, levels outside 1..CORR_MAX_LEVELS, a map too small for the levels, operands
+ * beyond 2^37 floats).
+ *
+ * flags: 0 = the library picks the path per workgroup; CORR_ONDEMAND_GENERAL forces the general
+ * path everywhere (so the two can be compared).
+ *   general: a wave per query and level gathers the rows of the (2r+2)^2 cells its taps touch and
+ *            forms the dot products with VALU fmaf.  Any radius, levels, D, coordinates.
+ *   tiled:   (radius <= 4) a workgroup owns an 8x8 block of queries of one batch item at one level,
+ *            stages the rows of the bounding box of their neighbourhoods in LDS and forms the
+ *            query x cell products on v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 fmaf chain).
+ *            Cap: the box (unclipped) holds at most 416 cells — 18x18 = 324 is uniform flow at
+ *            level 0 and radius 4; 20x20 fits.  A workgroup whose box exceeds the cap, or that
+ *            holds a query with far / non-finite coordinates or irregular taps (|coordinate|
+ *            near 2^20), takes the general path: the choice is a function of the coordinates
+ *            only, so results are deterministic run to run.
+ * The two paths sum the dot products in different orders: equal within the accuracy contract
+ * above, not bit for bit.  Inference only: there is no backward.
+ */
+#define CORR_ONDEMAND_GENERAL 1
+size_t corr_ondemand_workspace(int B, int D, int H, int W, int levels);
+int corr_ondemand_prepare(const float *fmap1, const float *fmap2, int B, int D, int H, int W, int levels,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int corr_ondemand_lookup(const void *workspace, const float *coords, int B, int D, int H, int W, int levels,
+                         int radius, int flags, float *out, void *stream);
 
 /*
  * Warm-start forward splat.  Replaces forward_interpolate_pytorch (utils/image_utils.py:52-83)

@@ -1,0 +1,145 @@
+"""On-demand lookup vs CorrBlock's build + lookups: one step = prepare (or build) + 12 lookups,
+captured as one HIP graph per variant and replayed; the variants of a size are alternated in ONE
+process on the same inputs, so box-to-box spread drops out.
+    python tools/bench_ondemand.py [--sizes dsec,hires1280,hires1920,uhd] [--trials 5] [--json PATH]
+Per size and coordinate kind (coherent = grid + smooth flow, what the GRU produces; sigma4 = grid +
+N(0, 4)): median ms per step of on-demand auto, on-demand forced-general and (where the pyramid
+fits) CorrBlock, each variant's peak device allocation, and the on-demand output's norm-relative
+difference from CorrBlock's.  Prints one JSON document; --json also writes it to a file."""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "e-raft_amd"))
+from eraft_amd import _lib  # noqa: E402
+from eraft_amd.corr import _alloc_pyramid  # noqa: E402
+
+# name: (H, W, CorrBlock fits)   B = 1, D = 256, 4 levels, r = 4, 12 lookups
+SIZES = {"dsec": (60, 80, True), "hires1280": (120, 160, True), "hires1920": (160, 240, True),
+         "uhd": (270, 480, False)}
+B, D, L, R, ITERS = 1, 256, 4, 4, 12
+
+
+def make_coords(kind, H, W, dev, gen):
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
+    base = torch.stack([xs, ys]).float()[None].repeat(B, 1, 1, 1)
+    out = []
+    for t in range(ITERS):
+        if kind == "coherent":  # a smooth flow field growing over the iterations, plus sub-pixel noise
+            fx = 3.0 * torch.sin(ys / H * math.pi) * (t + 1) / ITERS + 1.3
+            fy = -2.0 * torch.cos(xs / W * math.pi) * (t + 1) / ITERS - 0.6
+            flow = torch.stack([fx, fy])[None] + 0.05 * torch.randn(B, 2, H, W, device=dev, generator=gen)
+        else:
+            flow = 4.0 * torch.randn(B, 2, H, W, device=dev, generator=gen)
+        out.append((base + flow).contiguous())
+    return out
+
+
+def norm_rel(a, b):
+    return float((a - b).abs().max() / b.abs().max())
+
+
+def bench_size(name, trials, dev):
+    H, W, fits = SIZES[name]
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    f1 = torch.randn(B, D, H, W, device=dev, generator=gen)
+    f2 = torch.randn(B, D, H, W, device=dev, generator=gen)
+    K = (2 * R + 1) ** 2
+    stream = torch.cuda.Stream()
+    res = {"H": H, "W": W, "B": B, "D": D, "levels": L, "radius": R, "lookups": ITERS, "kinds": {}}
+    for kind in ("coherent", "sigma4"):
+        coords = make_coords(kind, H, W, dev, gen)
+        variants, graphs, peaks, outs, keep = {}, {}, {}, {}, []
+
+        def add(vname, alloc, step):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            state = alloc()
+            out = torch.empty(B, L * K, H, W, device=dev)
+            with torch.cuda.stream(stream):
+                step(state, out)
+                torch.cuda.synchronize()
+                outs[vname] = out.clone()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr, stream=stream):
+                    step(state, out)
+            torch.cuda.synchronize()
+            peaks[vname] = (torch.cuda.max_memory_allocated() - base - outs[vname].numel() * 4) / 1e6
+            graphs[vname] = gr
+            keep.append((state, out))
+
+        def od_step(flags):
+            def step(ws, out):
+                _lib.ondemand_prepare(f1, f2, L, ws)
+                for c in coords:
+                    _lib.ondemand_lookup(ws, c, D, L, R, out, flags)
+            return step
+
+        od_alloc = lambda: _lib.ondemand_workspace(B, D, H, W, L, dev)  # noqa: E731
+        add("ondemand_auto", od_alloc, od_step(0))
+        add("ondemand_general", od_alloc, od_step(_lib.ONDEMAND_GENERAL))
+        if fits:
+            algo = _lib.default_algo()
+
+            def cb_step(state, out):
+                pyr, ws = state
+                _lib.build(f1, f2, pyr, algo, ws)
+                for c in coords:
+                    _lib.lookup(pyr, c, R, out, H, W)
+
+            add("corrblock", lambda: (_alloc_pyramid(B, H, W, L, f1), _lib.build_workspace(f1, f2, algo)), cb_step)
+        steps = max(3, int(0.3 / (1e-3 * max(1.0, H * W / 4800.0))))  # ~0.3 s or more per window
+        times = {n: [] for n in graphs}
+        for t in range(trials + 1):
+            for n, gr in graphs.items():
+                gr.replay()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    gr.replay()
+                torch.cuda.synchronize()
+                if t:  # trial 0 warms every variant
+                    times[n].append((time.perf_counter() - t0) / steps * 1e3)
+        entry = {}
+        for n, v in times.items():
+            v = sorted(v)
+            entry[n] = {"step_ms_median": round(v[len(v) // 2], 4), "step_ms_min": round(v[0], 4),
+                        "step_ms_max": round(v[-1], 4), "peak_alloc_mb": round(peaks[n], 1)}
+        entry["auto_vs_general_rel"] = norm_rel(outs["ondemand_auto"], outs["ondemand_general"])
+        if fits:
+            entry["ondemand_vs_corrblock_rel"] = norm_rel(outs["ondemand_auto"], outs["corrblock"])
+        entry["steps_per_window"] = steps
+        res["kinds"][kind] = entry
+        del graphs, keep, outs
+        torch.cuda.empty_cache()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="dsec,hires1280,hires1920,uhd")
+    ap.add_argument("--trials", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_ondemand needs an MI355X (no CPU fallback)")
+    dev = torch.device("cuda", 0)
+    doc = {"device": torch.cuda.get_device_name(0), "step": "prepare/build + 12 lookups, one HIP graph",
+           "sizes": {n: bench_size(n, a.trials, dev) for n in a.sizes.split(",")}}
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
