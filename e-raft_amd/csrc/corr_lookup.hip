@@ -80,9 +80,11 @@ struct LookupSmem {
 // (window row rr, tile column tc): one 16-B load of the tile row holding cells (anchor_y + rr,
 // 4 (anchor_x / 4 + tc) .. + 3), zero outside the map; then four LDS stores realigned to the
 // window (unconditional: out-of-window cells go to the row's spare columns).  All of a thread's
-// loads are issued before any LDS store, so the gather costs one memory round trip.  The
-// query map bases are wave-uniform: qb is moved to a scalar register, so the 64-bit base
-// arithmetic is scalar.  TIGHT: only the rows / 16-B chunks the query's taps can touch (anchor ..
+// loads are issued before any LDS store, so the gather costs one memory round trip.  What
+// depends only on the lane is computed once per level, what depends only on the query once per
+// wave (all of its queries at once, lane k for query k, then readlane); per query and lane there
+// remain two selects, a mask test, the buffer load and the LDS stores (profiles/r07_lookup_gather.md:
+// 383 -> 309 VALU instructions per wave at DSEC).  TIGHT: only the rows / 16-B chunks the query's taps can touch (anchor ..
 // floor(last tap) + 1 on each axis: floors are monotone in the tap index) are loaded — a regular
 // window is 10 x 10 of the 11 x 11 neighbourhood; uncovered and far queries load all of it.  The
 // cells not loaded are written as zeros and never read.  NOLOAD: ablation (tools/kbench_lookup.hip).
@@ -96,74 +98,126 @@ __device__ __forceinline__ void gather_window_tiled(LookupSmem<S, QB> &sm, const
     constexpr int NW = NT / 64;
     constexpr int QPW = (QB + NW - 1) / NW;  // queries per wave
     static_assert(QPW <= 64, "one lane per query of the wave");
-    const unsigned TW = (unsigned)map_tiles(Wl);  // 16-B chunks per map row
-    const int TC = map_tcols(Wl);                  // tiles per map row
+    static_assert(NTC <= 5 && WIN <= 17, "the packed lane predicate holds 5 chunk and 17 row bits");
+    const int TW = map_tiles(Wl);   // 16-B chunks per map row
+    const int TC = map_tcols(Wl);   // tiles per map row
     const int lane = tid & 63;
-    int rr[EPL], tc[EPL];
+    const int wu = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned qb = __builtin_amdgcn_readfirstlane((unsigned)qbase);
+    // ---- lane constants (per level, not per query) ----
+    // The chunk of lane (rr, tc) of a query anchored at (X0, Y0) = (4 sX + a, 4 sY + y3) lies at
+    // byte   64 (sY TC + sX) + 16 y3                        wave-uniform: added to the query's base
+    //      + 64 tc + 16 rr + ((y3 + rr) >> 2) (64 TC - 64)    lane term: (y3 + rr) >> 2 is rr >> 2, plus
+    // one when (rr & 3) + y3 carries, so it is one of two lane constants (offA, and offA + tile row
+    // step).  pbit: the lane's chunk-column bit (0..4) and row bit (8..24) of the query's predicate
+    // word; bit 31 (never set in a predicate word) for lanes beyond the window.
+    const unsigned rstep = 64u * (unsigned)TC - 64u;
+    unsigned offA[EPL], offB[EPL], pbit[EPL];
+    int r3[EPL], tcl[EPL];
+    float *lrow[EPL];
 #pragma unroll
     for (int v = 0; v < EPL; ++v) {
         const int e = lane + 64 * v;
-        rr[v] = e / NTC;
-        tc[v] = e - rr[v] * NTC;
+        const int rr = e / NTC, tc = e - rr * NTC;
+        offA[v] = 64u * tc + 16u * rr + (unsigned)(rr >> 2) * rstep;
+        offB[v] = offA[v] + rstep;
+        asm volatile("" : "+v"(offB[v]));  // a register of its own: the choice below is one select, not select + add
+        pbit[v] = e < LPQ ? (1u << tc) | (1u << (8 + rr)) : 0x80000000u;
+        r3[v] = rr & 3;
+        tcl[v] = tc;
+        lrow[v] = &sm.win[wu * WQ + rr * WW + 4 * tc + 3];
     }
-    // The query a wave handles at step k is wave-uniform: all of the wave's anchors are read from
-    // LDS at once (lane k holds query k's) and moved to scalar registers with readlane.
-    const int wu = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned qb = __builtin_amdgcn_readfirstlane((unsigned)qbase);
-    int myX = kFarAnchor, myY = kFarAnchor, myE = WIN | (WIN << 8);
+    // ---- per query, computed for all of the wave's queries at once: lane k = query wu + NW k ----
+    // word: bits 0..4 the chunk columns inside the map (and, TIGHT, touched by the taps), 5..7 the
+    // chunk column that holds the map's last cells (7: none), 8..24 the rows likewise, 26..27 y3,
+    // 28..29 a; qoff: the wave-uniform byte offset.  Far, dead and fully outside queries: no bits.
+    unsigned word = 0;
+    int qoff = 0;
     {
         const int qq = wu + NW * lane;
         if (lane < QPW && qq < QB && n0 + qq < N) {
-            myX = sm.ax[qq];
-            myY = sm.ay[qq];
-            if (TIGHT && myX != kFarAnchor && myY != kFarAnchor) {
-                const float fx0 = sm.fx[0][qq], fxl = sm.fx[1][qq], fy0 = sm.ty[0][0][qq], fyl = sm.ty[0][S - 1][qq];
-                if (window_covers<S>(fx0, fxl, fy0, fyl)) myE = ((int)(fxl - fx0) + 2) | (((int)(fyl - fy0) + 2) << 8);
-            }
-        }
-    }
-    f32x4 vals[QPW][EPL];
-#pragma unroll
-    for (int k = 0; k < QPW; ++k) {
-        const int qq = wu + NW * k;
-        const int X0 = __builtin_amdgcn_readlane(myX, k);
-        const int Y0 = __builtin_amdgcn_readlane(myY, k);
-        const float *Pq = P + (size_t)(qb + (unsigned)qq) * mapsz;
-        int nx = WIN, ny = WIN;
-        if (TIGHT) {
-            const int E = __builtin_amdgcn_readlane(myE, k);
-            nx = (E & 255) + (X0 & 3), ny = E >> 8;  // chunk columns start at X0 & ~3
-        }
-#pragma unroll
-        for (int v = 0; v < EPL; ++v) {
-            const unsigned T = (unsigned)((X0 >> 2) + tc[v]), Y = (unsigned)(Y0 + rr[v]);
-            const bool need = !TIGHT || (rr[v] < ny && 4 * tc[v] < nx);
-            const bool ok = (lane + 64 * v < LPQ) && need && T < TW && Y < (unsigned)Hl;
-            vals[k][v] = (ok && !NOLOAD) ? *reinterpret_cast<const f32x4 *>(Pq + map_row4((int)Y, (int)T, TC))
-                                         : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-    const bool ragged = (Wl & 3) != 0;  // the last tile column holds cells past W_l: zero them
-#pragma unroll
-    for (int k = 0; k < QPW; ++k) {
-        const int qq = wu + NW * k;
-        const int X0 = __builtin_amdgcn_readlane(myX, k);
-        if (qq >= QB) continue;
-#pragma unroll
-        for (int v = 0; v < EPL; ++v) {
-            if (lane + 64 * v < LPQ) {
-                f32x4 x = vals[k][v];
-                if (ragged) {
-                    const int xb = ((X0 >> 2) + tc[v]) * 4;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) x[c] = xb + c < Wl ? x[c] : 0.0f;
+            const int X0 = sm.ax[qq], Y0 = sm.ay[qq];
+            if (X0 != kFarAnchor && Y0 != kFarAnchor) {
+                const int sX = X0 >> 2, a = X0 & 3, sY = Y0 >> 2, y3 = Y0 & 3;
+                int xhi = TW - sX, yhi = Hl - Y0;
+                if (TIGHT) {
+                    const float fx0 = sm.fx[0][qq], fxl = sm.fx[1][qq], fy0 = sm.ty[0][0][qq], fyl = sm.ty[0][S - 1][qq];
+                    if (window_covers<S>(fx0, fxl, fy0, fyl)) {  // chunk columns start at X0 & ~3
+                        xhi = min(xhi, ((int)(fxl - fx0) + 2 + a + 3) >> 2);
+                        yhi = min(yhi, (int)(fyl - fy0) + 2);
+                    } else {
+                        xhi = min(xhi, (WIN + a + 3) >> 2);
+                    }
                 }
-                float *row = &sm.win[qq * WQ + rr[v] * WW + 4 * tc[v] + 3 - (X0 & 3)];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) row[c] = x[c];
+                const int xlo = min(max(-sX, 0), NTC), ylo = min(max(-Y0, 0), WIN);
+                xhi = min(max(xhi, xlo), NTC), yhi = min(max(yhi, ylo), WIN);
+                const unsigned cols = ((1u << (xhi - xlo)) - 1u) << xlo, rows = ((1u << (yhi - ylo)) - 1u) << ylo;
+                const unsigned tl = (unsigned)(TW - 1 - sX) < (unsigned)NTC ? (unsigned)(TW - 1 - sX) : 7u;
+                word = (unsigned)a << 28;
+                if (cols != 0 && rows != 0) {
+                    word |= cols | (tl << 5) | (rows << 8) | ((unsigned)y3 << 26);
+                    qoff = (int)(64u * (unsigned)(sY * TC + sX) + 16u * (unsigned)y3);
+                }
             }
         }
     }
+    // ---- loads: all of a wave's queries before any LDS store ----
+    // One buffer load per lane and query through a descriptor based at the query's map plus qoff
+    // (scalar arithmetic): lanes outside the map or the window get an offset past the
+    // descriptor's range and read 0.0f without a branch; map cells pass through untouched.
+    const char *qmap = reinterpret_cast<const char *>(P) + (size_t)(qb + (unsigned)wu) * mapsz * 4;
+    const size_t qstep = (size_t)NW * mapsz * 4;
+    constexpr unsigned kPast = 0x80000000u;  // = the descriptor's range
+    f32x4 vals[QPW][EPL];
+    float *row[QPW][EPL];  // the LDS destination, realigned to the window: column 4 tc + 3 - a
+#pragma unroll
+    for (int k = 0; k < QPW; ++k) {
+        const unsigned wk = (unsigned)__builtin_amdgcn_readlane((int)word, k);
+        const int qk = __builtin_amdgcn_readlane(qoff, k);
+        const int c3 = 4 - (int)((wk >> 26) & 3u);
+        // (the realignment stays on the store side: one scalar-plus-lane add per query, and the
+        // window rows keep the odd query stride that makes the lane = query reads conflict-free;
+        // opaque, so the four stores share this one address and take immediate offsets)
+        int shift = k * NW * WQ - (int)((wk >> 28) & 3u);
+        asm volatile("" : "+s"(shift));
+#pragma unroll
+        for (int v = 0; v < EPL; ++v) {
+            row[k][v] = lrow[v] + shift;
+            if (NOLOAD) {
+                vals[k][v] = f32x4{0.f, 0.f, 0.f, 0.f};
+                continue;
+            }
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<char *>(qmap + (size_t)k * qstep + (ptrdiff_t)qk), 0, (int)kPast, 0x00020000);
+            const unsigned off = r3[v] >= c3 ? offB[v] : offA[v];
+            const unsigned voff = (wk & pbit[v]) == pbit[v] ? off : kPast;
+            vals[k][v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
+        }
+    }
+    // ---- LDS stores ----
+    auto store_all = [&](auto rag) {
+        constexpr bool RAGGED = decltype(rag)::value;
+        const int wr = Wl & 3;
+#pragma unroll
+        for (int v = 0; v < EPL; ++v) {
+            if (lane + 64 * v >= LPQ) continue;
+#pragma unroll
+            for (int k = 0; k < QPW; ++k) {
+                if (wu + NW * k >= QB) continue;
+                f32x4 x = vals[k][v];
+                if (RAGGED) {  // the map's last chunk column holds cells past W_l: zero them
+                    const unsigned wk = (unsigned)__builtin_amdgcn_readlane((int)word, k);
+                    const bool last = tcl[v] == (int)((wk >> 5) & 7u);
+#pragma unroll
+                    for (int c = 1; c < 4; ++c) x[c] = (last && c >= wr) ? 0.0f : x[c];
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) row[k][v][c] = x[c];
+            }
+        }
+    };
+    if ((Wl & 3) != 0) store_all(std::true_type{});
+    else store_all(std::false_type{});
 }
 
 constexpr int lookup_threads(int S, int QB) { return (QB * S + 63) / 64 * 64; }
@@ -185,7 +239,7 @@ __device__ __forceinline__ void lookup_block_v(LookupSmem<S, QB> &sm, const floa
     using SM = LookupSmem<S, QB>;
     constexpr int WIN = SM::WIN, WW = SM::WW, WQ = SM::WQ;
     const int Hl = H >> l, Wl = W >> l;
-    const float inv_scale = 1.0f / (float)(1 << l);
+    const float inv_scale = __uint_as_float((unsigned)(127 - l) << 23);  // 2^-l, exactly (no division sequence)
     const unsigned mapsz = (unsigned)map_floats(Hl, Wl);
     const int TC = map_tcols(Wl);
     const size_t qbase = (size_t)b * N + n0;
@@ -217,9 +271,10 @@ __device__ __forceinline__ void lookup_block_v(LookupSmem<S, QB> &sm, const floa
     if (act) {
         const int ax0 = sm.ax[q], ay0 = sm.ay[q];
         const bool far = ax0 == kFarAnchor || ay0 == kFarAnchor;
-        const bool covers = window_covers<S>(sm.fx[0][q], sm.fx[1][q], sm.ty[0][0][q], sm.ty[0][S - 1][q]);
         const bool reg = far || (tx.f == (float)(ax0 + i) && ty.f == (float)(ay0 + i));
-        const int f = (covers ? 0 : 1) | (reg ? 0 : 2);
+        int f = reg ? 0 : 2;
+        // covering is a property of the query: its tap-0 threads test it (one wave, not all)
+        if (i == 0 && !window_covers<S>(sm.fx[0][q], sm.fx[1][q], sm.ty[0][0][q], sm.ty[0][S - 1][q])) f |= 1;
         if (f) atomicOr(&sm.flags, f);
     }
 
@@ -314,6 +369,9 @@ __global__ __launch_bounds__(lookup_threads(S, QB)) void lookup_kernel(
     const int n0 = __builtin_amdgcn_readfirstlane((blockIdx.x - b * nqb) * QB);
     const int l = blockIdx.y;
     const int i = threadIdx.x / QB, n = n0 + threadIdx.x % QB;
+    // (a scalar base per store plus a 32-bit thread offset saves ~20 VALU per wave here, but the
+    // stores then measured slower: DSEC 5.22 -> 5.31 us, train 9.68 -> 9.84; a 32-bit thread offset
+    // into the 64-bit pointer alone is a wash; profiles/r07_lookup_gather.md)
     float *o = out + (((size_t)b * L + l) * K + (size_t)i * S) * N + n;
     lookup_block<S, QB, NT, ABL, TIGHT>(sm, pyr.p[l], coords, b, n0, N, H, W, l, (int)threadIdx.x, [&](int j, float acc) {
         // non-temporal: the output streams past L2 (nothing in this kernel re-reads it), so the

@@ -73,7 +73,8 @@ def main():
                 res[n].append((time.perf_counter() - t0) / steps * 1e3)
     for n, v in res.items():
         v = sorted(v)
-        print(f"{wl} {n}: step median {v[len(v) // 2]:.4f} ms  min {v[0]:.4f}  ({B / v[len(v) // 2] * 1e3:.0f} pairs/s)")
+        print(f"{wl} {n}: step median {v[len(v) // 2]:.4f} ms  min {v[0]:.4f}  spread (max - min) {v[-1] - v[0]:.4f}  "
+              f"({B / v[len(v) // 2] * 1e3:.0f} pairs/s)")
     _lib._lib = libs["cur"]
     return 0 if same else 1
 
