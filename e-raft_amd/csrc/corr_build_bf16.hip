@@ -43,6 +43,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <type_traits>
 
 #include "corr_build_common.h"
 
@@ -70,6 +71,27 @@ constexpr int kPixBytes = kStepK * kPieces * 2;         // workspace bytes per p
 struct Geom {
     int S, NQp, NQB, NQG, Hp, CB, Wp;
 };
+
+// Lane swaps of a register pair (v_permlane16_swap_b32 / v_permlane32_swap_b32).  swap32(x, z):
+// lanes 32-63 of x trade with lanes 0-31 of z.  swap16(x, z): the same per pair of 16-lane rows —
+// the odd rows of x trade with the even rows of z.  Either way the low half keeps its x and
+// receives its partner's x in z, the high half keeps its z and receives its partner's z in x.
+// Inline asm: hipcc 7.2 lowers __builtin_amdgcn_permlane{16,32}_swap's two results to the first
+// register twice.  The compiler inserts no wait states around inline asm, so each block opens
+// with the two a swap needs after a VALU write of one of its registers (s_nop 1); the x4 forms
+// pay them once for four swaps.
+#define CORR_SWAP_FNS(N)                                                                                               \
+    __device__ __forceinline__ void swap##N(float &x, float &z) {                                                      \
+        asm volatile("s_nop 1\n\tv_permlane" #N "_swap_b32 %0, %1" : "+v"(x), "+v"(z));                                \
+    }                                                                                                                  \
+    __device__ __forceinline__ void swap##N##x4(float (&x)[4], float (&z)[4]) {                                        \
+        asm volatile("s_nop 1\n\tv_permlane" #N "_swap_b32 %0, %4\n\tv_permlane" #N "_swap_b32 %1, %5\n\t"             \
+            "v_permlane" #N "_swap_b32 %2, %6\n\tv_permlane" #N "_swap_b32 %3, %7"                                     \
+            : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(z[0]), "+v"(z[1]), "+v"(z[2]), "+v"(z[3]));         \
+    }
+CORR_SWAP_FNS(16)
+CORR_SWAP_FNS(32)
+#undef CORR_SWAP_FNS
 
 inline Geom geom(int D, int NQ, int H, int W) {
     Geom g;
@@ -222,10 +244,12 @@ __device__ __forceinline__ Tile xcd_block_tile(const Args &p, int t) {
 // compiler's own wait on them then also covers the next step's query loads, which have landed
 // by then).  ACC2 = false: the six products of a K step chained from zero into a transient and
 // added to one accumulator by VALU (four query slots) — the same rounding count, measured slower.
-// VF (measurement variants, tools/kbench_build.hip; 0 in the library): bit 0 = query loads by
+// VF (variants, tools/kbench_build.hip; the library runs kLibVF): bit 0 = query loads by
 // inline asm (the compiler then adds no wait of its own on them), bit 1 = s_setprio 1 over the
-// K loop (the epilogue of a neighbouring workgroup yields issue slots to MFMA-phase waves), bit 2 =
-// no half-patch body (padding rows computed and discarded: one kernel body).
+// K loop (the epilogue of a neighbouring workgroup yields issue slots to MFMA-phase waves:
+// neutral under the shfl_xor epilogue, -5 % of the DSEC step under the lane-swap one,
+// profiles/r08_build_epilogue.md), bit 2 = no half-patch body (padding rows computed and
+// discarded: one kernel body).
 // (8 waves per workgroup — 256 queries against the patch, so its LDS-DMA records feed twice the
 // MFMAs and the L2 operand traffic per flop drops by a quarter, one workgroup per CU — was
 // measured and dropped: bit-identical, 5-15 % slower at every size,
@@ -434,86 +458,142 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
     // Every pool is ((a + b) + c) + d in avg_pool2d's order (bit-identical).  A store runs whenever
     // its tile row lies in the padded map (cells past W_l / H_l are padding: the zero-padded target
     // records make them finite, nothing reads them).
+    // Every trade is "keep one register, give the other, take the partner's": one lane swap
+    // (swap16 / swap32) on the register pair, after which both lane parities hold the kept value
+    // in the first register and the partner's in the second — no permute through LDS, no selects.
     const int H = p.H, W = p.W, NQ = p.NQ, nlev = FAST ? 4 : p.nlev;
     const int H1 = H >> 1, W1 = W >> 1, H2 = H >> 2, W2 = W >> 2, H3 = H >> 3, W3 = W >> 3;
     const int TC0 = map_tcols(W), TC1 = map_tcols(W1), TC2 = map_tcols(W2), TC3 = map_tcols(W3);
     const int R0 = 4 * map_tiles(H), R1 = 4 * map_tiles(H1), R2 = 4 * map_tiles(H2), R3 = 4 * map_tiles(H3);
     const size_t M0 = map_floats(H, W), M1 = map_floats(H1, W1), M2 = map_floats(H2, W2), M3 = map_floats(H3, W3);
     const int h = grp >> 1, k = grp & 1;
-    float l2s[2][2];  // level 2 of both query blocks: (Y2 = h, X2 = 2k + j)
+
+    // The two accumulators meet, scaled in place: acc[i][rp][c] becomes patch cell
+    // (4 (rp >> 2) + grp, 4 (rp & 3) + c) of query block i — the level-0 store operand as it
+    // stands.  split_sum differs from hi + lo only where hi is infinite, so the wave takes the
+    // per-element form only when one of its accumulators is (fmaxf drops a NaN operand, and a NaN
+    // hi gives a NaN sum either way); rows >= NR are zero on both paths.
+    if constexpr (ACC2) {
+        float big = 0.f;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int q = (qb0 + i) * 16 + ci;
-        const bool qok = q < NQ;
-        const size_t qrow = (size_t)b * NQ + q;
-        float v[kPatchRows][4];  // v[rp][c]: patch cell (4 (rp >> 2) + grp, 4 (rp & 3) + c)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < kPatchRows; ++r)
+            for (int r = 0; r < NR; ++r)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) v[r][g] = (ACC2 ? split_sum(acc[i][r][g], acs[i][r][g]) : acc[i][r][g]) * p.inv_s;
-        if (qok && nlev > 0) {
-            float *m0 = p.lvl[0] + qrow * M0;
+                for (int g = 0; g < 4; ++g) big = __builtin_fmaxf(big, __builtin_fabsf(acc[i][r][g]));
+        if (__builtin_amdgcn_ballot_w64(__builtin_isinf(big)) != 0) {
 #pragma unroll
-            for (int rp = 0; rp < kPatchRows; ++rp) {
-                const int Y = y0 + 4 * (rp >> 2) + grp, T = (x0 >> 2) + (rp & 3);
-                if (Y < R0 && 4 * T < W)
-                    *reinterpret_cast<float4 *>(m0 + map_row4(Y, T, TC0)) = make_float4(v[rp][0], v[rp][1], v[rp][2], v[rp][3]);
-            }
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) acc[i][r][g] = split_sum(acc[i][r][g], acs[i][r][g]) * p.inv_s;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < NR; ++r) acc[i][r] = (acc[i][r] + acs[i][r]) * p.inv_s;
         }
-        float l1[2][4];  // l1[tr][m]: level-1 cell (2 tr + h, 4k + m) of the patch
+    } else {
 #pragma unroll
-        for (int tr = 0; tr < 2; ++tr) {
-            float top[2][4], bot[2][4];  // rows 2h, 2h + 1 of tiles 4 tr + 2k + j
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int r = 0; r < NR; ++r) acc[i][r] = acc[i][r] * p.inv_s;
+    }
+
+    // Interior (wave-uniform): every store of every level lies inside its padded map and the
+    // wave's 32 queries all exist — the stores then run straight-line, unpredicated.  (A level-0
+    // row is always inside: a full body has y0 + 4 < H, so R0 >= y0 + 8; a half body stores rows
+    // y0 .. y0 + 3 only, its rows 4-7 lie at or past R0.)
+    const bool interior = (qb0 + 2) * 16 <= NQ && y0 + NR <= R0 && x0 + 12 < W &&
+                          (nlev < 2 || ((y0 >> 1) + 4 <= R1 && 4 * ((x0 >> 3) + 1) < W1)) &&
+                          (nlev < 3 || ((y0 >> 2) + 2 <= R2 && (x0 >> 2) < W2)) &&
+                          (nlev < 4 || ((y0 >> 3) < R3 && (x0 >> 3) + 1 < kTileW * TC3));
+
+    // EDGE: the predicated stores (a second copy of the pooling and store section, never of the K loop).
+    auto pool_store = [&](auto edge) __attribute__((always_inline)) {
+        constexpr bool EDGE = decltype(edge)::value;
+        float l2s[2][2];  // level 2 of both query blocks: (Y2 = h, X2 = 2k + j)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float mine = k ? v[4 * tr + 2 + j][c] : v[4 * tr + j][c];
-                    const float give = k ? v[4 * tr + j][c] : v[4 * tr + 2 + j][c];
-                    const float got = __shfl_xor(give, 16);
-                    top[j][c] = k ? got : mine;
-                    bot[j][c] = k ? mine : got;
+        for (int i = 0; i < 2; ++i) {
+            const int q = (qb0 + i) * 16 + ci;
+            const bool qok = !EDGE || q < NQ;
+            const size_t qrow = (size_t)b * NQ + q;
+            if (nlev > 0) {
+                // one per-lane base per query block; a block's stores differ by tile-uniform steps:
+                // 64 B per tile within a tile row, 64 TC0 B per tile row
+                float *m0 = p.lvl[0] + qrow * M0 + map_row4(y0 + grp, x0 >> 2, TC0);
+#pragma unroll
+                for (int rp = 0; rp < NR; ++rp) {
+                    float *dst = m0 + ((rp >> 2) * TC0 + (rp & 3)) * (4 * kTileW);
+                    if (!EDGE || (qok && y0 + 4 * (rp >> 2) + grp < R0 && 4 * ((x0 >> 2) + (rp & 3)) < W))
+                        *reinterpret_cast<f32x4_t *>(dst) = acc[i][rp];
                 }
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int j = m >> 1, c = 2 * (m & 1);
-                l1[tr][m] = pool4(top[j][c], top[j][c + 1], bot[j][c], bot[j][c + 1]);
             }
-            const int Y1 = (y0 >> 1) + 2 * tr + h, T1 = (x0 >> 3) + k;
-            if (qok && nlev > 1 && Y1 < R1 && 4 * T1 < W1)
-                *reinterpret_cast<float4 *>(p.lvl[1] + qrow * M1 + map_row4(Y1, T1, TC1)) =
-                    make_float4(l1[tr][0], l1[tr][1], l1[tr][2], l1[tr][3]);
-        }
-        // level 2 (Y2 = h, X2 = 2k + j): level-1 rows 2h (lane (0, k), tr = h) and 2h + 1 (lane (1, k))
-        float top[4], bot[4];
+            float l1[2][4];  // l1[tr][m]: level-1 cell (2 tr + h, 4k + m) of the patch
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float give = h ? l1[0][m] : l1[1][m];
-            const float got = __shfl_xor(give, 32);
-            top[m] = h ? got : l1[0][m];
-            bot[m] = h ? l1[1][m] : got;
-        }
+            for (int tr = 0; tr < 2; ++tr) {
+                if (4 * tr < NR) {
+                    // rows 2h, 2h + 1 of tiles 4 tr + 2k + j: X = tile 4 tr + j, Z = tile 4 tr + 2 + j;
+                    // swap16(X, Z) leaves the top row in X and the bottom row in Z for k = 0 and 1 alike
+                    float top[2][4], bot[2][4];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) l2s[i][j] = pool4(top[2 * j], top[2 * j + 1], bot[2 * j], bot[2 * j + 1]);
-    }
-    {
-        // Level 2 rows of BOTH blocks, one 16-B store per lane: lane (h, k) stores row h of block k;
-        // lanes (h, 0), (h, 1) hold columns 0-1 / 2-3 and trade the other block's pair.
-        const float g0 = __shfl_xor(k ? l2s[0][0] : l2s[1][0], 16), g1 = __shfl_xor(k ? l2s[0][1] : l2s[1][1], 16);
-        const float o0 = k ? l2s[1][0] : l2s[0][0], o1 = k ? l2s[1][1] : l2s[0][1];
-        const float4 o = k ? make_float4(g0, g1, o0, o1) : make_float4(o0, o1, g0, g1);
-        const int q = (qb0 + k) * 16 + ci, Y2 = (y0 >> 2) + h;
-        if (q < NQ && nlev > 2 && Y2 < R2 && (x0 >> 2) < W2)
-            *reinterpret_cast<float4 *>(p.lvl[2] + ((size_t)b * NQ + q) * M2 + map_row4(Y2, x0 >> 4, TC2)) = o;
-    }
-    {
-        // Level 3, cell X3 = k of block h: level-2 rows 0 (lanes (0, k)) and 1 (lanes (1, k)).
-        const float g0 = __shfl_xor(h ? l2s[0][0] : l2s[1][0], 32), g1 = __shfl_xor(h ? l2s[0][1] : l2s[1][1], 32);
-        const float l3 = h ? pool4(g0, g1, l2s[1][0], l2s[1][1]) : pool4(l2s[0][0], l2s[0][1], g0, g1);
-        const int q = (qb0 + h) * 16 + ci;
-        const int Y3 = y0 >> 3, X3 = (x0 >> 3) + k;
-        if (q < NQ && nlev > 3 && Y3 < R3 && X3 < kTileW * TC3) p.lvl[3][((size_t)b * NQ + q) * M3 + map_cell(Y3, X3, TC3)] = l3;
-    }
+                    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) top[j][c] = acc[i][4 * tr + j][c], bot[j][c] = acc[i][4 * tr + 2 + j][c];
+                        swap16x4(top[j], bot[j]);
+                    }
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        const int j = m >> 1, c = 2 * (m & 1);
+                        l1[tr][m] = pool4(top[j][c], top[j][c + 1], bot[j][c], bot[j][c + 1]);
+                    }
+                } else {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) l1[tr][m] = 0.f;  // a half patch's rows 4-7: pools of zeros
+                }
+            }
+            if (nlev > 1) {
+                // level-1 rows 2 tr + h share a tile: 32 B apart
+                float *m1 = p.lvl[1] + qrow * M1 + map_row4((y0 >> 1) + h, (x0 >> 3) + k, TC1);
+#pragma unroll
+                for (int tr = 0; tr < 2; ++tr)
+                    if (!EDGE || (qok && (y0 >> 1) + 2 * tr + h < R1 && 4 * ((x0 >> 3) + k) < W1))
+                        *reinterpret_cast<f32x4_t *>(m1 + 2 * tr * kTileW) = f32x4_t{l1[tr][0], l1[tr][1], l1[tr][2], l1[tr][3]};
+            }
+            // level 2 (Y2 = h, X2 = 2k + j): level-1 rows 2h (lane (0, k), tr = h) and 2h + 1 (lane
+            // (1, k)); swap32(l1[0], l1[1]) leaves the top row in l1[0] and the bottom row in l1[1]
+            swap32x4(l1[0], l1[1]);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) l2s[i][j] = pool4(l1[0][2 * j], l1[0][2 * j + 1], l1[1][2 * j], l1[1][2 * j + 1]);
+        }
+        {
+            // Level 2 rows of BOTH blocks, one 16-B store per lane: lane (h, k) stores row h of block k;
+            // lanes (h, 0), (h, 1) hold columns 0-1 / 2-3 and trade the other block's pair: after
+            // swap16(block 0's, block 1's) the row is (first, second) on both.
+            float a0 = l2s[0][0], a1 = l2s[0][1], c0 = l2s[1][0], c1 = l2s[1][1];
+            swap16(a0, c0);
+            swap16(a1, c1);
+            const int q = (qb0 + k) * 16 + ci, Y2 = (y0 >> 2) + h;
+            if (nlev > 2 && (!EDGE || (q < NQ && Y2 < R2 && (x0 >> 2) < W2)))
+                *reinterpret_cast<f32x4_t *>(p.lvl[2] + ((size_t)b * NQ + q) * M2 + map_row4(Y2, x0 >> 4, TC2)) =
+                    f32x4_t{a0, a1, c0, c1};
+        }
+        {
+            // Level 3, cell X3 = k of block h: level-2 rows 0 (lanes (0, k)) and 1 (lanes (1, k)); after
+            // swap32(block 0's, block 1's) the pool reads (first, second) on both.
+            float a0 = l2s[0][0], a1 = l2s[0][1], c0 = l2s[1][0], c1 = l2s[1][1];
+            swap32(a0, c0);
+            swap32(a1, c1);
+            const float l3 = pool4(a0, a1, c0, c1);
+            const int q = (qb0 + h) * 16 + ci;
+            const int Y3 = y0 >> 3, X3 = (x0 >> 3) + k;
+            if (nlev > 3 && (!EDGE || (q < NQ && Y3 < R3 && X3 < kTileW * TC3)))
+                p.lvl[3][((size_t)b * NQ + q) * M3 + map_cell(Y3, X3, TC3)] = l3;
+        }
+    };
+    if (interior) pool_store(std::false_type{});
+    else pool_store(std::true_type{});
 }
 
 template <int SS, bool ACC2 = true, int VF = 0, bool FAST = false>
@@ -541,7 +621,9 @@ inline Ws workspace_of(void *ws, int B, const Geom &g) {
     return r;
 }
 
-template <int SS, bool ACC2 = true, int VF = 0>
+constexpr int kLibVF = 2;  // the library's VF: K loop at priority 1
+
+template <int SS, bool ACC2 = true, int VF = kLibVF>
 hipError_t launch_kernel(dim3 grid, const Args &p, hipStream_t s) {
     const bool fast = p.nlev == 4;
     static std::atomic<unsigned long long> lds_done[2];
@@ -597,7 +679,7 @@ hipError_t launch_pack(const float *f1, int NQ, const float *f2, int B, int D, i
 
 // The MFMA part (operands already packed in ws).  levels == 0: the MFMAs and epilogue
 // arithmetic without stores (measurement).  variant (tools/kbench_build.hip A/B, D = 256 only):
-// 1 = the single-accumulator form (ACC2 = false), 2..4 = VF 1..3, 5 = VF 4.
+// 1 = the single-accumulator form (ACC2 = false), 2..4 = VF 1..3, 5 = VF 4, 6 = VF 0.
 // y0, y1: the target region (as launch_pack), whose pyramid rows [y0 >> l, ceil(y1 / 2^l)) of
 // every level it writes.
 hipError_t launch_mfma(int NQ, int B, int D, int H, int W, int levels, const LevelPtrs &pyr, void *ws,
@@ -633,11 +715,12 @@ hipError_t launch_mfma(int NQ, int B, int D, int H, int W, int levels, const Lev
     if (variant != 0) {
         if (g.S != 8) return hipErrorInvalidValue;
         switch (variant) {
-            case 1: e = launch_kernel<8, false>(grid, p, s); break;
+            case 1: e = launch_kernel<8, false, 0>(grid, p, s); break;
             case 2: e = launch_kernel<8, true, 1>(grid, p, s); break;
             case 3: e = launch_kernel<8, true, 2>(grid, p, s); break;
             case 4: e = launch_kernel<8, true, 3>(grid, p, s); break;
             case 5: e = launch_kernel<8, true, 4>(grid, p, s); break;
+            case 6: e = launch_kernel<8, true, 0>(grid, p, s); break;
             default: return hipErrorInvalidValue;
         }
     } else switch (g.S <= 8 ? g.S : 0) {

@@ -145,8 +145,8 @@ int main(int argc, char **argv) {
         vs.push_back({"bf16x6 mfma tchain NOSTORE", [&](float *o) {
                           return bf16b::launch_mfma(NQ, sh.B, sh.D, sh.H, sh.W, 0, lp_of(o), wsbf, 0, 1);
                       }, false});
-        for (int vv : {2, 3, 5}) {
-            const char *nm[] = {"", "", "bf16x6 mfma hiddenQ", "bf16x6 mfma prio", "bf16x6 mfma hiddenQ+prio", "bf16x6 mfma no half path"};
+        for (int vv : {2, 3, 5, 6}) {
+            const char *nm[] = {"", "", "bf16x6 mfma hiddenQ", "bf16x6 mfma prio", "bf16x6 mfma hiddenQ+prio", "bf16x6 mfma no half path", "bf16x6 mfma no prio"};
             vs.push_back({nm[vv], [&, vv](float *o) {
                               return bf16b::launch_mfma(NQ, sh.B, sh.D, sh.H, sh.W, 4, lp_of(o), wsbf, 0, vv);
                           }, false});
@@ -242,7 +242,7 @@ int main(int argc, char **argv) {
             same("1-tile no half path", [&](float *o) { return launch_split_mfma(NQ, sh.B, sh.D, sh.H, sh.W, 4, lp_of(o), ws, 0, true, 2); });
             same("1-tile nopipe", [&](float *o) { return launch_split_mfma(NQ, sh.B, sh.D, sh.H, sh.W, 4, lp_of(o), ws, 0, true, 1); });
             if (sh.D == 256) {
-                for (int vv : {2, 3, 5, 9, 10, 11}) {  // bf16x6 variants vs the default bf16x6 kernel (9: tile order 2; 10: order 0 gq 16; 11: order 1 gq 32)
+                for (int vv : {2, 3, 5, 6, 9, 10, 11}) {  // bf16x6 variants vs the default bf16x6 kernel (9: tile order 2; 10: order 0 gq 16; 11: order 1 gq 32)
                     CK(launch_build_bf16(f1, NQ, f2, sh.B, sh.D, sh.H, sh.W, 4, lp_of(ref), wsbf, 0, 0));
                     CK(hipMemset(out, 0xff, tot * 4));
                     CK(vv == 9    ? bf16b::launch_mfma(NQ, sh.B, sh.D, sh.H, sh.W, 4, lp_of(out), wsbf, 0, 0, 2)
