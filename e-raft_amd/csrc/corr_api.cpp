@@ -425,6 +425,40 @@ int corr_ondemand_lookup(const void *workspace, const float *coords, int B, int 
         launch_ondemand_lookup(workspace, coords, B, D, H, W, levels, radius, flags, out, (hipStream_t)stream), fn);
 }
 
+size_t corr_ondemand_bwd_workspace(int B, int D, int H, int W, int levels, int radius) {
+    if (check_ondemand("corr_ondemand_bwd_workspace", B, D, H, W, levels) ||
+        check_radius("corr_ondemand_bwd_workspace", radius))
+        return 0;
+    return ondemand_bwd_workspace_bytes(B, D, H, W, levels, radius);
+}
+
+int corr_ondemand_backward(const void *fwd_workspace, const float *const *coords, const float *const *grads, int T,
+                           int B, int D, int H, int W, int levels, int radius, void *bwd_workspace,
+                           size_t bwd_workspace_bytes, float *dfmap1, float *dfmap2, void *stream) {
+    static const char *fn = "corr_ondemand_backward";
+    g_err[0] = 0;
+    int rc = check_ondemand(fn, B, D, H, W, levels);
+    if (rc || (rc = check_radius(fn, radius))) return rc;
+    if (T < 1) return fail(CORR_EINVAL, "%s: T must be >= 1 (got %d)", fn, T);
+    if (!fwd_workspace) return fail(CORR_EINVAL, "%s: fwd_workspace is NULL", fn);
+    if ((uintptr_t)fwd_workspace % 16) return fail(CORR_EINVAL, "%s: fwd_workspace is not 16-byte aligned", fn);
+    if (!bwd_workspace) return fail(CORR_EINVAL, "%s: bwd_workspace is NULL", fn);
+    if ((uintptr_t)bwd_workspace % 16) return fail(CORR_EINVAL, "%s: bwd_workspace is not 16-byte aligned", fn);
+    if (!coords || !grads) return fail(CORR_EINVAL, "%s: coords / grads arrays are NULL", fn);
+    for (int t = 0; t < T; ++t)
+        if ((rc = check_ptr(fn, coords[t], "coords[t]")) || (rc = check_ptr(fn, grads[t], "grads[t]"))) return rc;
+    if (!dfmap1 && !dfmap2) return fail(CORR_EINVAL, "%s: dfmap1 and dfmap2 are both NULL", fn);
+    if ((dfmap1 && (rc = check_ptr(fn, dfmap1, "dfmap1"))) || (dfmap2 && (rc = check_ptr(fn, dfmap2, "dfmap2"))))
+        return rc;
+    const size_t need = ondemand_bwd_workspace_bytes(B, D, H, W, levels, radius);
+    if (!need) return fail(CORR_EINVAL, "%s: H and W must be <= 65536 (got %d, %d)", fn, H, W);
+    if (bwd_workspace_bytes < need)
+        return fail(CORR_EINVAL, "%s: bwd_workspace of %zu bytes needed, got %zu", fn, need, bwd_workspace_bytes);
+    return hip_status(launch_ondemand_backward(fwd_workspace, coords, grads, T, B, D, H, W, levels, radius,
+                                               bwd_workspace, dfmap1, dfmap2, (hipStream_t)stream),
+                      fn);
+}
+
 size_t corr_lookup_conv_weights_bytes(void) { return lookup_conv_weights_bytes(); }
 
 int corr_lookup_conv_weights(const float *weight, int out_channels, int in_channels, void *packed, void *stream) {

@@ -176,6 +176,12 @@ hipError_t launch_ondemand_prepare(const float *f1, const float *f2, int B, int 
                                    hipStream_t s);
 hipError_t launch_ondemand_lookup(const void *ws, const float *coords, int B, int D, int H, int W, int levels,
                                   int radius, int flags, float *out, hipStream_t s);
+// Its backward (corr_ondemand_bwd.hip): accumulator rows and one lookup's window blocks in `bwd_ws`;
+// df1 / df2 may be null (that side is skipped).  0 bytes = sizes the backward does not accept.
+size_t ondemand_bwd_workspace_bytes(int B, int D, int H, int W, int levels, int radius);
+hipError_t launch_ondemand_backward(const void *fwd_ws, const float *const *coords, const float *const *grads, int T,
+                                    int B, int D, int H, int W, int levels, int radius, void *bwd_ws, float *df1,
+                                    float *df2, hipStream_t s);
 size_t build_bwd_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bwd(const float *grad_c, const float *f1, int NQ, const float *f2, int B,
                             int D, int H, int W, float *df1, float *df2, float *ws, hipStream_t s);

@@ -45,41 +45,14 @@
 #include "corr_build_common.h"
 #include "corr_common.h"
 #include "corr_div.h"
+#include "corr_ondemand_common.h"
 #include "corr_taps.h"
 
 namespace corr {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kOdWaves = 4;               // waves per workgroup
-constexpr int kOdQPW = 4;                 // queries per wave (in sequence)
-constexpr int kOdQB = kOdWaves * kOdQPW;  // queries per workgroup
-constexpr int kOdMaxS = 2 * CORR_MAX_RADIUS + 1;
 constexpr int kOdMaxCells = (kOdMaxS + 1) * (kOdMaxS + 1);
 constexpr int kOdChunk = 64;  // 16-B pieces of a row held in registers at a time (256 features)
-
-inline int padded_d(int D) { return (D + 3) & ~3; }
-
-struct OdLayout {
-    size_t f1;                       // float offset of the fmap1 rows
-    size_t p[CORR_MAX_LEVELS];       // float offset of pooled level l's rows
-    size_t total;                    // floats in all
-};
-
-inline OdLayout ondemand_offsets(int B, int D, int H, int W, int levels) {
-    OdLayout o{};
-    const size_t Dp = (size_t)padded_d(D);
-    size_t at = 0;
-    o.f1 = at;
-    at += (size_t)B * H * W * Dp;
-    for (int l = 0; l < levels; ++l) {
-        o.p[l] = at;
-        at += (size_t)B * (H >> l) * (W >> l) * Dp;
-    }
-    o.total = at;
-    return o;
-}
 
 // [B][D][N] -> [B][N][Dp] for fmap1 and fmap2 (one launch): 32 x 32 tiles through LDS, reads
 // coalesced along n, writes along d; channels D .. Dp-1 are written as zeros.
@@ -135,14 +108,6 @@ struct OdSmem {
     float cell[kOdWaves][kOdMaxCells];     // a wave's query's neighbourhood, [cy (S+1) + cx]
     float tap[kOdWaves][6][kOdMaxS + 1];   // x: f, lo, hi; y: f, lo, hi
 };
-
-// LDS hand-over between the lanes of one wave: a wave's DS operations execute in order, so
-// only the compiler has to be kept from moving accesses across this point.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b, float acc) {
     acc = __builtin_fmaf(a[0], b[0], acc);
@@ -324,8 +289,6 @@ constexpr int kTlMaxS = 9, kTlQ = 64, kTlNT = 13, kTlCells = 32 * kTlNT /* 416 *
 constexpr int kTlRows = kTlQ + kTlCells, kTlRS = kTlRows + 2;  // row stride = 2 mod 8: conflict-free staging writes
 constexpr int kTlWS = (kTlMaxS + 1) * (kTlMaxS + 1) + 1;       // odd stride: lane = query reads conflict-free
 constexpr int kTlItems = (kTlRows * (kTlDK / 4) + 255) / 256;   // staged 16-B pieces per thread and chunk
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct TlSmem {
     union {

@@ -31,7 +31,8 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_voxel_grid_tbilinear", "corr_lookup_bwd_multi", "corr_pool_fold", "corr_backward_workspace",
            "corr_backward", "corr_convex_upsample_bwd_workspace", "corr_convex_upsample_bwd", "corr_build_region",
            "corr_lookup_conv_bwd_workspace", "corr_lookup_conv_bwd", "corr_map_floats", "corr_pyramid_export",
-           "corr_pyramid_import", "corr_ondemand_workspace", "corr_ondemand_prepare", "corr_ondemand_lookup")
+           "corr_pyramid_import", "corr_ondemand_workspace", "corr_ondemand_prepare", "corr_ondemand_lookup",
+           "corr_ondemand_bwd_workspace", "corr_ondemand_backward")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -139,7 +140,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_ondemand_workspace.restype = sz
     lib.corr_ondemand_prepare.argtypes = [vp, vp, i, i, i, i, i, vp, sz, vp]
     lib.corr_ondemand_lookup.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp]
-    for f in ("corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
+    lib.corr_ondemand_bwd_workspace.argtypes = [i, i, i, i, i, i]
+    lib.corr_ondemand_bwd_workspace.restype = sz
+    lib.corr_ondemand_backward.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, sz, vp, vp, vp]
+    for f in ("corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
@@ -574,3 +578,48 @@ def ondemand_lookup(workspace, coords, D, levels, radius, out, flags=0):
         raise ValueError(f"out has {out.numel()} floats, the lookup writes {B}x{levels * K}x{H * W}")
     with torch.cuda.device(coords.device):
         _check(lib.corr_ondemand_lookup(ws, c, B, D, H, W, levels, radius, flags, o, _stream(coords)))
+
+
+def ondemand_bwd_workspace(B, D, H, W, levels, radius, device):
+    """A device workspace for corr_ondemand_backward (accumulator rows + one lookup's window blocks)."""
+    n = load().corr_ondemand_bwd_workspace(B, D, H, W, levels, radius)
+    if n == 0:
+        raise CorrError(CORR_EINVAL, f"corr_ondemand_bwd_workspace: unsupported sizes B={B} D={D} {H}x{W}, "
+                                     f"{levels} levels, radius {radius}")
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def ondemand_backward(fwd_workspace, coords_list, grad_list, D, levels, radius, bwd_workspace=None, want1=True,
+                      want2=True):
+    """corr_ondemand_backward: (dfmap1, dfmap2) [B, D, H, W] of one prepared workspace and its lookups
+    (coords_list[t] [B, 2, H, W], grad_list[t] [B, levels*K, H, W], in order).  A side that is not
+    wanted is skipped and returned as None."""
+    if len(coords_list) != len(grad_list) or not coords_list:
+        raise ValueError("coords_list and grad_list must hold the same number (>= 1) of lookups")
+    if not (want1 or want2):
+        raise ValueError("at least one of dfmap1 / dfmap2 must be wanted")
+    B, _, H, W = coords_list[0].shape
+    K = (2 * radius + 1) ** 2
+    for c, g in zip(coords_list, grad_list):
+        if tuple(c.shape) != (B, 2, H, W) or tuple(g.shape) != (B, levels * K, H, W):
+            raise ValueError(f"lookup shapes {tuple(c.shape)} / {tuple(g.shape)} do not match "
+                             f"[{B}, 2, {H}, {W}] / [{B}, {levels * K}, {H}, {W}]")
+    lib = load()
+    fws = _dev(fwd_workspace, "fwd_workspace")
+    if fwd_workspace.numel() * 4 < lib.corr_ondemand_workspace(B, D, H, W, levels):
+        raise ValueError("fwd_workspace is smaller than corr_ondemand_workspace for these sizes")
+    if bwd_workspace is None:
+        bwd_workspace = ondemand_bwd_workspace(B, D, H, W, levels, radius, fwd_workspace.device)
+    bws = _dev(bwd_workspace, "bwd_workspace")
+    need = lib.corr_ondemand_bwd_workspace(B, D, H, W, levels, radius)
+    if need == 0 or bwd_workspace.numel() * 4 < need:
+        raise ValueError("bwd_workspace is smaller than corr_ondemand_bwd_workspace for these sizes")
+    cp, gp = _ptrs(coords_list, "coords"), _ptrs(grad_list, "grads")
+    dev = fwd_workspace.device
+    df1 = torch.empty((B, D, H, W), dtype=torch.float32, device=dev) if want1 else None
+    df2 = torch.empty((B, D, H, W), dtype=torch.float32, device=dev) if want2 else None
+    with torch.cuda.device(dev):
+        _check(lib.corr_ondemand_backward(fws, cp, gp, len(coords_list), B, D, H, W, levels, radius, bws,
+                                          bwd_workspace.numel() * 4, None if df1 is None else df1.data_ptr(),
+                                          None if df2 is None else df2.data_ptr(), _stream(fwd_workspace)))
+    return df1, df2

@@ -225,7 +225,7 @@ class ERAFT(nn.Module):
         if self.subtype not in ("standard", "warm_start"):
             raise ValueError(f"unknown subtype {self.subtype}")
         # RAFT's switch: lookups computed from the feature maps (OnDemandCorrBlock; no all-pairs
-        # volume, inference only) instead of CorrBlock.  Config key, default off;
+        # volume; its backward works without one too) instead of CorrBlock.  Config key, default off;
         # ERAFT_AMD_ONDEMAND=1 / =0 overrides it.
         alt = bool(config.get("alternate_corr", False)) if hasattr(config, "get") else False
         env = os.environ.get("ERAFT_AMD_ONDEMAND")
@@ -261,8 +261,11 @@ class ERAFT(nn.Module):
         image1 = self.image_padder.pad(image1).contiguous()
         image2 = self.image_padder.pad(image2).contiguous()
         fmap1, fmap2 = self.fnet([image1, image2])
-        block = OnDemandCorrBlock if self.alternate_corr else CorrBlock
-        corr_fn = block(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius)
+        if self.alternate_corr:
+            corr_fn = OnDemandCorrBlock(fmap1.float(), fmap2.float(), num_levels=self.corr_levels,
+                                        radius=self.corr_radius, train=torch.is_grad_enabled())
+        else:
+            corr_fn = CorrBlock(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius)
         net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)
         n, _, h, w = image1.shape

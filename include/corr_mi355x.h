@@ -65,7 +65,8 @@ extern "C" {
  *        reference's results for non-finite inputs (+-inf where fp32 has +-inf; NaN only where it
  *        has NaN) instead of NaN for every output an infinity reaches.
  *        Added under 202 (purely additive, no version change): corr_ondemand_workspace,
- *        corr_ondemand_prepare, corr_ondemand_lookup. */
+ *        corr_ondemand_prepare, corr_ondemand_lookup; corr_ondemand_bwd_workspace,
+ *        corr_ondemand_backward. */
 int corr_version(void);
 
 /* Thread-local description of the last error on this thread ("" if none). */
@@ -328,7 +329,7 @@ int corr_backward(int algo, const float *const *coords_rows, const float *const 
  *            near 2^20), takes the general path: the choice is a function of the coordinates
  *            only, so results are deterministic run to run.
  * The two paths sum the dot products in different orders: equal within the accuracy contract
- * above, not bit for bit.  Inference only: there is no backward.
+ * above, not bit for bit.  The backward is corr_ondemand_backward (below).
  */
 #define CORR_ONDEMAND_GENERAL 1
 size_t corr_ondemand_workspace(int B, int D, int H, int W, int levels);
@@ -336,6 +337,39 @@ int corr_ondemand_prepare(const float *fmap1, const float *fmap2, int B, int D, 
                           void *workspace, size_t workspace_bytes, void *stream);
 int corr_ondemand_lookup(const void *workspace, const float *coords, int B, int D, int H, int W, int levels,
                          int radius, int flags, float *out, void *stream);
+
+/*
+ * The on-demand lookup's backward: dfmap1 / dfmap2 of one corr_ondemand_prepare and its T lookups
+ * (coords[t], grads[t] = the upstream gradient of lookup t, [B][levels*K][H*W]; host arrays of
+ * device pointers, processed in list order), without the all-pairs volume or its gradient.  With
+ * Wg_t[b][n][l][cell] = the sum, over the taps and corners of query n that land on `cell` inside
+ * H_l x W_l, of corner weight * grads[t][b][l*K + i*(2r+1) + j][n] (the forward's weights):
+ *   dF1[b][n][:]     = 1/sqrt(D) * sum_t sum_l sum_cell Wg_t[b][n][l][cell] * P_l[b][cell][:]
+ *   dP_l[b][cell][:] = 1/sqrt(D) * sum_t sum_n Wg_t[b][n][l][cell] * F1[b][n][:]
+ *   dfmap2 = dP_0 + poolT(dP_1 + poolT(dP_2 + ...))   (a coarse cell gives 0.25 of itself to each of
+ *            its four children; rows / columns dropped by the floor halving receive nothing)
+ * i.e. autograd of the lookups above with respect to both feature maps (there is no gradient to the
+ * coordinates).  Far, NaN and +-inf coordinates and one-cell levels contribute nothing, as in
+ * corr_backward.  fp32 throughout, no float atomics, a fixed summation order: reruns are
+ * bit-identical.  dfmap1 / dfmap2 ([B][D][H][W], overwritten) may each be NULL: that side's work is
+ * skipped; both NULL is an error.
+ *
+ * fwd_workspace: as prepared by corr_ondemand_prepare for the same B, D, H, W, levels.
+ * bwd_workspace: 16-byte aligned, uninitialised, >= corr_ondemand_bwd_workspace bytes,
+ * Dp = D rounded up to a multiple of 4, S = 2*radius + 1:
+ *   float dF1rows[B][H*W][Dp]; for l = 0 .. levels-1: float dProws_l[B][H_l*W_l][Dp];
+ *   for l = 1 .. levels-1: float part_l[seg_l][B][H_l*W_l][Dp], seg_l = min(4^l, 64)   (the dP gather
+ *   cuts a coarse level's queries into seg_l segments; one lookup's partial sums, reused);
+ *   int origin[B][levels][H*W][2]; float block[B][levels][H*W][(S+2)*(S+2)]   (one lookup's, reused)
+ * = 4 * B * (Dp * (H*W + sum_l H_l*W_l + sum_{l>=1} seg_l*H_l*W_l) + levels * H*W * ((S+2)*(S+2) + 2))
+ * bytes, e.g. 285 MB at 160x240, D = 256, 4 levels, radius 4 (CorrBlock's training there holds the
+ * 7.9 GB pyramid and as much again of its gradient).  corr_ondemand_bwd_workspace returns 0 for the sizes
+ * corr_ondemand_workspace rejects, a radius outside 0..CORR_MAX_RADIUS, and H or W above 65536.
+ */
+size_t corr_ondemand_bwd_workspace(int B, int D, int H, int W, int levels, int radius);
+int corr_ondemand_backward(const void *fwd_workspace, const float *const *coords, const float *const *grads, int T,
+                           int B, int D, int H, int W, int levels, int radius, void *bwd_workspace,
+                           size_t bwd_workspace_bytes, float *dfmap1, float *dfmap2, void *stream);
 
 /*
  * Warm-start forward splat.  Replaces forward_interpolate_pytorch (utils/image_utils.py:52-83)

@@ -5,7 +5,13 @@ process on the same inputs, so box-to-box spread drops out.
 Per size and coordinate kind (coherent = grid + smooth flow, what the GRU produces; sigma4 = grid +
 N(0, 4)): median ms per step of on-demand auto, on-demand forced-general and (where the pyramid
 fits) CorrBlock, each variant's peak device allocation, and the on-demand output's norm-relative
-difference from CorrBlock's.  Prints one JSON document; --json also writes it to a file."""
+difference from CorrBlock's.  Prints one JSON document; --json also writes it to a file.
+    python tools/bench_ondemand.py --train [--sizes ...] [--json profiles/ondemand_train_bench.json]
+--train: one step = prepare (or build) + 12 lookups + the backward to both feature maps
+(corr_ondemand_backward / corr_backward) with coherent coordinates and gauss upstream gradients,
+on-demand against CorrBlock (where the pyramid and its gradient fit) in the same way; also the
+on-demand step's split: forward only, and the backward to fmap1 only / fmap2 only (the window
+kernel alone / the window kernel without dF1 plus the dP gather)."""
 import argparse
 import json
 import math
@@ -18,7 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "e-raft_amd"))
 from eraft_amd import _lib  # noqa: E402
-from eraft_amd.corr import _alloc_pyramid  # noqa: E402
+from eraft_amd.corr import _alloc_grad_pyramid, _alloc_pyramid  # noqa: E402
 
 # name: (H, W, CorrBlock fits)   B = 1, D = 256, 4 levels, r = 4, 12 lookups
 SIZES = {"dsec": (60, 80, True), "hires1280": (120, 160, True), "hires1920": (160, 240, True),
@@ -122,17 +128,110 @@ def bench_size(name, trials, dev):
     return res
 
 
+def bench_train(name, trials, dev):
+    """Training steps at one size: {variant: ms per step, peak allocation}, gradients' difference."""
+    H, W, fits = SIZES[name]
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    f1 = torch.randn(B, D, H, W, device=dev, generator=gen)
+    f2 = torch.randn(B, D, H, W, device=dev, generator=gen)
+    K = (2 * R + 1) ** 2
+    coords = make_coords("coherent", H, W, dev, gen)
+    grads = [torch.randn(B, L * K, H, W, device=dev, generator=gen) for _ in range(ITERS)]
+    out = torch.empty(B, L * K, H, W, device=dev)  # the lookups' output (its values are not kept)
+    stream = torch.cuda.Stream()
+    graphs, peaks, results, keep = {}, {}, {}, []
+
+    def add(vname, alloc, step):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        state = alloc()
+        with torch.cuda.stream(stream):
+            results[vname] = step(state)
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr, stream=stream):
+                keep.append(step(state))
+        torch.cuda.synchronize()
+        peaks[vname] = (torch.cuda.max_memory_allocated() - base) / 1e6
+        graphs[vname] = gr
+        keep.append(state)
+
+    def od_alloc():
+        ws = _lib.ondemand_workspace(B, D, H, W, L, dev)
+        _lib.ondemand_prepare(f1, f2, L, ws)  # the backward-only variants read it
+        return (ws, _lib.ondemand_bwd_workspace(B, D, H, W, L, R, dev))
+
+    def od_step(fwd, want1, want2):
+        def step(state):
+            ws, bws = state
+            if fwd:
+                _lib.ondemand_prepare(f1, f2, L, ws)
+                for c in coords:
+                    _lib.ondemand_lookup(ws, c, D, L, R, out)
+            if want1 or want2:
+                return _lib.ondemand_backward(ws, coords, grads, D, L, R, bws, want1=want1, want2=want2)
+        return step
+
+    add("ondemand", od_alloc, od_step(True, True, True))
+    add("ondemand_forward_only", od_alloc, od_step(True, False, False))
+    add("ondemand_backward_dfmap1_only", od_alloc, od_step(False, True, False))
+    add("ondemand_backward_dfmap2_only", od_alloc, od_step(False, False, True))
+    if fits:
+        algo = _lib.default_algo()
+
+        def cb_step(state):
+            pyr, ws, gl = state
+            _lib.build(f1, f2, pyr, algo, ws)
+            for c in coords:
+                _lib.lookup(pyr, c, R, out, H, W)
+            return _lib.backward(coords, grads, R, gl, f1, f2)
+
+        add("corrblock", lambda: (_alloc_pyramid(B, H, W, L, f1), _lib.build_workspace(f1, f2, algo),
+                                  _alloc_grad_pyramid(B, H, W, L, f1)), cb_step)
+    steps = max(2, int(0.3 / (6e-3 * max(1.0, H * W / 4800.0))))
+    times = {n: [] for n in graphs}
+    for t in range(trials + 1):
+        for n, gr in graphs.items():
+            gr.replay()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                gr.replay()
+            torch.cuda.synchronize()
+            if t:  # trial 0 warms every variant
+                times[n].append((time.perf_counter() - t0) / steps * 1e3)
+    res = {"H": H, "W": W, "B": B, "D": D, "levels": L, "radius": R, "lookups": ITERS, "coords": "coherent",
+           "steps_per_window": steps}
+    for n, v in times.items():
+        v = sorted(v)
+        res[n] = {"step_ms_median": round(v[len(v) // 2], 4), "step_ms_min": round(v[0], 4),
+                  "step_ms_max": round(v[-1], 4), "peak_alloc_mb": round(peaks[n], 1)}
+    if fits:
+        res["dfmap1_vs_corrblock_rel"] = norm_rel(results["ondemand"][0], results["corrblock"][0])
+        res["dfmap2_vs_corrblock_rel"] = norm_rel(results["ondemand"][1], results["corrblock"][1])
+    del graphs, keep, results
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="dsec,hires1280,hires1920,uhd")
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--train", action="store_true", help="training steps: forward + backward to both maps")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_ondemand needs an MI355X (no CPU fallback)")
     dev = torch.device("cuda", 0)
-    doc = {"device": torch.cuda.get_device_name(0), "step": "prepare/build + 12 lookups, one HIP graph",
-           "sizes": {n: bench_size(n, a.trials, dev) for n in a.sizes.split(",")}}
+    if a.train:
+        doc = {"device": torch.cuda.get_device_name(0),
+               "step": "prepare/build + 12 lookups + backward to both maps, one HIP graph",
+               "sizes": {n: bench_train(n, a.trials, dev) for n in a.sizes.split(",")}}
+    else:
+        doc = {"device": torch.cuda.get_device_name(0), "step": "prepare/build + 12 lookups, one HIP graph",
+               "sizes": {n: bench_size(n, a.trials, dev) for n in a.sizes.split(",")}}
     text = json.dumps(doc, indent=1)
     print(text)
     if a.json:
