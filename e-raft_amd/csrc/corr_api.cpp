@@ -527,6 +527,62 @@ int corr_lookup_conv_bwd(const float *const *pyr, const float *coords, int B, in
                       fn);
 }
 
+static int check_gru_channels(const char *fn, int hidden, int input) {
+    if (!gru_supported(hidden, input))
+        return fail(CORR_EUNSUPPORTED,
+                    "%s: built for hidden = 128 and hidden + input a multiple of 32, <= 1024 (got %d, %d)", fn, hidden,
+                    input);
+    return CORR_OK;
+}
+
+size_t corr_gru_weights_bytes(int hidden, int input) {
+    if (!gru_supported(hidden, input)) return 0;
+    return gru_weights_bytes(hidden, input);
+}
+
+int corr_gru_pack_weights(const float *wz, const float *wr, const float *wq, int hidden, int input, void *packed,
+                          void *stream) {
+    static const char *fn = "corr_gru_pack_weights";
+    g_err[0] = 0;
+    int rc;
+    if ((rc = check_gru_channels(fn, hidden, input))) return rc;
+    if ((rc = check_ptr(fn, wz, "wz")) || (rc = check_ptr(fn, wr, "wr")) || (rc = check_ptr(fn, wq, "wq")) ||
+        (rc = check_ptr(fn, packed, "packed")))
+        return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_gru_pack(wz, wr, wq, hidden, input, packed, (hipStream_t)stream), fn);
+}
+
+size_t corr_gru_workspace(int B, int hidden, int H, int W) {
+    if (B < 1 || hidden < 1 || H < 1 || W < 1) return 0;
+    return gru_workspace(B, hidden, H, W);
+}
+
+int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
+                       const void *packed, const float *bz, const float *br, const float *bq, void *workspace,
+                       size_t workspace_bytes, float *h_out, void *stream) {
+    static const char *fn = "corr_gru_half_step";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    if ((rc = check_gru_channels(fn, hidden, input))) return rc;
+    if (dir != 0 && dir != 1) return fail(CORR_EINVAL, "%s: dir must be 0 (1x5) or 1 (5x1) (got %d)", fn, dir);
+    if ((rc = check_ptr(fn, h, "h")) || (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, bz, "bz")) ||
+        (rc = check_ptr(fn, br, "br")) || (rc = check_ptr(fn, bq, "bq")) || (rc = check_ptr(fn, h_out, "h_out")))
+        return rc;
+    if (input > 0 && (rc = check_ptr(fn, x, "x"))) return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if (h_out == h || h_out == x) return fail(CORR_EINVAL, "%s: h_out must not alias h or x", fn);
+    const size_t need = gru_workspace(B, hidden, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(CORR_EINVAL, "%s: workspace of %zu bytes needed, got %zu", fn, need, workspace_bytes);
+    if ((uintptr_t)workspace % 16) return fail(CORR_EINVAL, "%s: workspace is not 16-byte aligned", fn);
+    return hip_status(launch_gru_half_step(h, x, B, hidden, input, H, W, dir, packed, bz, br, bq, workspace, h_out,
+                                           (hipStream_t)stream),
+                      fn);
+}
+
 int corr_convex_upsample(const float *flow, const float *mask, int N, int h, int w, float *out, void *stream) {
     static const char *fn = "corr_convex_upsample";
     g_err[0] = 0;

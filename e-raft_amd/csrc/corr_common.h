@@ -182,6 +182,15 @@ size_t ondemand_bwd_workspace_bytes(int B, int D, int H, int W, int levels, int 
 hipError_t launch_ondemand_backward(const void *fwd_ws, const float *const *coords, const float *const *grads, int T,
                                     int B, int D, int H, int W, int levels, int radius, void *bwd_ws, float *df1,
                                     float *df2, hipStream_t s);
+// SepConvGRU half step (corr_gru.hip): the weight pack, then gates + candidate launches.
+bool gru_supported(int hidden, int input);
+size_t gru_weights_bytes(int hidden, int input);
+size_t gru_workspace(int B, int hidden, int H, int W);
+hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, int hidden, int input, void *packed,
+                           hipStream_t s);
+hipError_t launch_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
+                                const void *packed, const float *bz, const float *br, const float *bq, void *ws,
+                                float *h_out, hipStream_t s);
 size_t build_bwd_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bwd(const float *grad_c, const float *f1, int NQ, const float *f2, int B,
                             int D, int H, int W, float *df1, float *df2, float *ws, hipStream_t s);

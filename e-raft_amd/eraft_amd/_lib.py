@@ -32,7 +32,8 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_backward", "corr_convex_upsample_bwd_workspace", "corr_convex_upsample_bwd", "corr_build_region",
            "corr_lookup_conv_bwd_workspace", "corr_lookup_conv_bwd", "corr_map_floats", "corr_pyramid_export",
            "corr_pyramid_import", "corr_ondemand_workspace", "corr_ondemand_prepare", "corr_ondemand_lookup",
-           "corr_ondemand_bwd_workspace", "corr_ondemand_backward")
+           "corr_ondemand_bwd_workspace", "corr_ondemand_backward", "corr_gru_weights_bytes",
+           "corr_gru_pack_weights", "corr_gru_workspace", "corr_gru_half_step")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -143,7 +144,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_ondemand_bwd_workspace.argtypes = [i, i, i, i, i, i]
     lib.corr_ondemand_bwd_workspace.restype = sz
     lib.corr_ondemand_backward.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, sz, vp, vp, vp]
-    for f in ("corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
+    lib.corr_gru_weights_bytes.argtypes, lib.corr_gru_weights_bytes.restype = [i, i], sz
+    lib.corr_gru_pack_weights.argtypes = [vp, vp, vp, i, i, vp, vp]
+    lib.corr_gru_workspace.argtypes, lib.corr_gru_workspace.restype = [i, i, i, i], sz
+    lib.corr_gru_half_step.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp, vp]
+    for f in ("corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
@@ -623,3 +628,42 @@ def ondemand_backward(fwd_workspace, coords_list, grad_list, D, levels, radius, 
                                           bwd_workspace.numel() * 4, None if df1 is None else df1.data_ptr(),
                                           None if df2 is None else df2.data_ptr(), _stream(fwd_workspace)))
     return df1, df2
+
+
+def gru_pack_weights(wz, wr, wq):
+    """corr_gru_pack_weights: the three gate weights [hidden, C, 1, 5] or [hidden, C, 5, 1] (each
+    [hidden][C][5] when contiguous) -> the packed split (an opaque buffer)."""
+    ws = [w.detach().contiguous().float() for w in (wz, wr, wq)]
+    hidden, C = ws[0].shape[0], ws[0].shape[1]
+    for w in ws:
+        if w.dim() != 4 or w.shape[0] != hidden or w.shape[1] != C or w.shape[2] * w.shape[3] != 5:
+            raise ValueError(f"GRU gate weights must be [hidden, C, 1, 5] or [hidden, C, 5, 1] "
+                             f"(got {[tuple(v.shape) for v in ws]})")
+    lib = load()
+    n = lib.corr_gru_weights_bytes(hidden, C - hidden)
+    if n == 0:
+        raise CorrError(CORR_EUNSUPPORTED, f"corr_gru_weights_bytes: unsupported hidden = {hidden}, C = {C}")
+    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=ws[0].device)
+    with torch.cuda.device(ws[0].device):
+        _check(lib.corr_gru_pack_weights(_dev(ws[0], "wz"), _dev(ws[1], "wr"), _dev(ws[2], "wq"), hidden, C - hidden,
+                                         packed.data_ptr(), _stream(ws[0])))
+    return packed
+
+
+def gru_half_step(h, x, direction, packed, bz, br, bq, workspace=None):
+    """corr_gru_half_step: h [B, hidden, H, W], x [B, input, H, W] -> the new h (allocated here).
+    direction 0 = the 1x5 gates, 1 = the 5x1 ones; packed from gru_pack_weights."""
+    B, hidden, H, W = h.shape
+    if x.dim() != 4 or x.shape[0] != B or tuple(x.shape[2:]) != (H, W):
+        raise ValueError(f"x {tuple(x.shape)} does not match h {tuple(h.shape)}")
+    lib = load()
+    hp, xp, pk = _dev(h, "h"), _dev(x, "x"), _dev(packed, "packed")
+    need = lib.corr_gru_workspace(B, hidden, H, W)
+    if workspace is None:
+        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=h.device)
+    out = torch.empty_like(h)
+    with torch.cuda.device(h.device):
+        _check(lib.corr_gru_half_step(hp, xp, B, hidden, x.shape[1], H, W, direction, pk, _dev(bz, "bz"),
+                                      _dev(br, "br"), _dev(bq, "bq"), _dev(workspace, "workspace"),
+                                      workspace.numel() * 4, out.data_ptr(), _stream(h)))
+    return out

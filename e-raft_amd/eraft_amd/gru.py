@@ -1,0 +1,53 @@
+"""SepConvGRU on the MI355X: each half step is corr_gru_half_step (two HIP launches on the bf16
+MFMA with the exact three-piece split, csrc/corr_gru.hip) instead of six MIOpen convolutions,
+four cats and the elementwise kernels between them.  Inference only: there is no backward, so
+model.SepConvGRU takes this path only when autograd is not recording.
+"""
+from __future__ import annotations
+
+import weakref
+
+import torch
+
+from . import _lib
+
+_GRU_PACKS = {}  # ids of (wz, wr, wq) -> (weakrefs to them, their (data_ptr, _version)s, pack)
+
+
+def _gru_pack(wz, wr, wq):
+    """The packed split of one half step's three gate weights, cached with corr._weight_pack's
+    scheme: keyed by the tensors' ids, held by weak references (nothing is attached to the
+    Parameters, and the entry goes when any of them does), together with the (data_ptr,
+    _version) triple it was made from, so another module's tensors never see this pack and an
+    in-place update (optimizer step, load_state_dict's copy_) re-packs."""
+    ws = (wz, wr, wq)
+    ids = tuple(id(w) for w in ws)
+    key = tuple((w.data_ptr(), w._version) for w in ws)
+    ent = _GRU_PACKS.get(ids)
+    if ent is None or any(r() is not w for r, w in zip(ent[0], ws)) or ent[1] != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("sepconv_gru: the GRU weights must be packed before a graph capture "
+                               "(run one forward outside the capture first)")
+        drop = lambda _r, ids=ids: _GRU_PACKS.pop(ids, None)
+        ent = (tuple(weakref.ref(w, drop) for w in ws), key, _lib.gru_pack_weights(wz, wr, wq))
+        _GRU_PACKS[ids] = ent
+    return ent[2]
+
+
+def half_step(module, h, x, tag):
+    """One half step of `module` (a SepConvGRU): tag "1" = convz1/convr1/convq1 (1x5), "2" = the
+    5x1 ones."""
+    cz, cr, cq = (getattr(module, f"conv{g}{tag}") for g in "zrq")
+    packed = _gru_pack(cz.weight, cr.weight, cq.weight)
+    return _lib.gru_half_step(h, x, 0 if tag == "1" else 1, packed, cz.bias.detach(), cr.bias.detach(),
+                              cq.bias.detach())
+
+
+def sepconv_gru(module, h, x):
+    """SepConvGRU.forward (update.py:45-60) for a module with convz1 .. convq2: the horizontal,
+    then the vertical half step.  h [B, 128, H, W], x [B, input, H, W], fp32 on the GPU."""
+    for t, nm in ((h, "h"), (x, "x")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise RuntimeError(f"{nm} must be a tensor on an MI355X (HIP) device: eraft_amd has no CPU fallback")
+    h, x = h.detach().contiguous(), x.detach().contiguous()
+    return half_step(module, half_step(module, h, x, "1"), x, "2")

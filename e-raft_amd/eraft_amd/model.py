@@ -118,6 +118,11 @@ class BasicMotionEncoder(nn.Module):
 class SepConvGRU(nn.Module):
     """Horizontal (1x5) then vertical (5x1) convolutional GRU (update.py:34-61)."""
 
+    # ERAFT_AMD_FUSE_GRU=1: at inference on the MI355X each half step is corr_gru_half_step (two
+    # HIP launches on the bf16 MFMA, gru.py) instead of the torch / MIOpen chain below.  Default
+    # off (DESIGN §14 has the measurements); training always runs the torch code.
+    fused = os.environ.get("ERAFT_AMD_FUSE_GRU", "0") == "1"
+
     def __init__(self, hidden_dim=128, input_dim=192 + 128):
         super().__init__()
         c = hidden_dim + input_dim
@@ -132,7 +137,23 @@ class SepConvGRU(nn.Module):
         q = torch.tanh(getattr(self, f"convq{tag}")(torch.cat([r * h, x], dim=1)))
         return (1 - z) * h + z * q
 
+    def _fusable(self, h, x):
+        """The fused half steps (gru.sepconv_gru) are built for fp32 GPU tensors, hidden = 128 and
+        C a multiple of 32 (<= 1024), and have no backward."""
+        if not (h.is_cuda and x.is_cuda and h.dtype == x.dtype == torch.float32 and h.dim() == x.dim() == 4):
+            return False
+        hidden, c = h.shape[1], h.shape[1] + x.shape[1]
+        if hidden != 128 or c % 32 or c > 1024 or tuple(self.convz1.weight.shape) != (hidden, c, 1, 5):
+            return False
+        ps = list(self.parameters())
+        if len(ps) != 12 or any(p.dtype != torch.float32 or p.device != h.device for p in ps):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in (h, x, *ps)))
+
     def forward(self, h, x):
+        if self.fused and self._fusable(h, x):
+            from .gru import sepconv_gru
+            return sepconv_gru(self, h, x)
         return self._step(self._step(h, x, "1"), x, "2")
 
 

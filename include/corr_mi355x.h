@@ -471,6 +471,39 @@ int corr_convex_upsample_bwd(const float *flow, const float *mask, const float *
 int corr_forward_splat(const float *flow, int B, int H, int W, float *out, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/*
+ * One half step of the update block's SepConvGRU (model/update.py:45-60), inference only (no
+ * backward).  dir 0 = the horizontal 1x5 convolutions (padding (0,2)), dir 1 = the vertical 5x1
+ * ones (padding (2,0)); C = hidden + input:
+ *   z  = sigmoid(bz + convz([h, x]))        r = sigmoid(br + convr([h, x]))
+ *   q  = tanh(bq + convq([r*h, x]))         h_out = (1 - z) * h + z * q
+ * Layouts: h, h_out [B][hidden][H][W]; x [B][input][H][W] (h and x are two pointers, no cat);
+ * wz, wr, wq [hidden][C][5] (a contiguous (1,5) and a contiguous (5,1) Conv2d weight both are),
+ * tap t multiplies the pixel (t - 2) columns (dir 0) or rows (dir 1) away, zero outside the map;
+ * bz, br, bq [hidden].  All fp32, 4-byte aligned.
+ * Arithmetic: two launches (gates: z and r*h into the workspace, r is never stored; candidate:
+ * q and the blend).  Each convolution is an implicit GEMM with K = 5 C on the bf16 MFMA with
+ * CORR_BUILD_BF16X6's exact three-piece split (six products per fp32 product, no scales: no
+ * narrower than fp32), fp32 accumulation in a fixed order (32-channel chunk outer, tap inner), so
+ * results are deterministic.  sigmoid(v) = 1 / (1 + expf(-v)) and tanhf(v), each fp32 op rounded
+ * once.  Finite inputs give finite outputs; non-finite inputs are NOT parity-checked (an
+ * infinite activation meets the zero low pieces of the weights and comes out NaN).
+ * The weights are split once per weight version by corr_gru_pack_weights into a
+ * corr_gru_weights_bytes(hidden, input) buffer (16-B aligned, opaque; 0 for unsupported sizes).
+ * Workspace: corr_gru_workspace(B, hidden, H, W) bytes, 16-B aligned = z then r*h, each
+ * [B][hidden][H][W] fp32 rounded up to 256 bytes (0 when a size is < 1).  h_out must not alias
+ * h or x.  hidden = 128, C a multiple of 32 and <= 1024, any B, H, W >= 1 with B*H*W < 2^31;
+ * other channel counts return CORR_EUNSUPPORTED.  No allocation, no synchronisation; the
+ * launches go on `stream` and can be captured into a graph.
+ */
+size_t corr_gru_weights_bytes(int hidden, int input);
+int corr_gru_pack_weights(const float *wz, const float *wr, const float *wq, int hidden, int input, void *packed,
+                          void *stream);
+size_t corr_gru_workspace(int B, int hidden, int H, int W);
+int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
+                       const void *packed, const float *bz, const float *br, const float *bq, void *workspace,
+                       size_t workspace_bytes, float *h_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
