@@ -52,6 +52,30 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+template <int K, int N, class F>
+__device__ __forceinline__ void static_for(F f) {
+    if constexpr (K < N) {
+        f(std::integral_constant<int, K>{});
+        static_for<K + 1, N>(f);
+    }
+}
+
+// (p[O0], p[O1]) of LDS as one aligned register pair.  RD2: by one ds_read2_b32 (dword offsets
+// <= 255), which the compiler's wait counting does not see: the caller waits (lgkmcnt) before
+// the first use.
+template <bool RD2, int O0, int O1>
+__device__ __forceinline__ pk2 lds_pair(const float *p) {
+    if constexpr (RD2) {
+        static_assert(O0 >= 0 && O0 <= 255 && O1 >= 0 && O1 <= 255, "ds_read2_b32 offsets are 8 bits");
+        const unsigned a = (unsigned)(size_t)(const __attribute__((address_space(3))) float *)p;
+        pk2 r;
+        asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(r) : "v"(a), "n"(O0), "n"(O1) : "memory");
+        return r;
+    } else {
+        return pk2{p[O0], p[O1]};
+    }
+}
+
 // True when every in-map corner of the query's taps lies inside its (S+2)^2 neighbourhood.
 template <int S>
 __device__ __forceinline__ bool window_covers(float fx0, float fxl, float fy0, float fyl) {
@@ -73,8 +97,59 @@ struct LookupSmem {
     float ty[3][S][QB];
     float fx[2][QB];  // floor of x-tap 0 and S-1
     int ax[QB], ay[QB];
+    unsigned gw[QB];  // the gather's per-query words (gather_words), written by the tap-0 threads
+    int go[QB];
     int flags;
 };
+
+// kOpt bits: the lookup's instruction-count switches (tools/kbench_lookup.hip times each against
+// the forms they replace; profiles/r09_lookup_issue.md).  1: the gather's per-query words once per
+// workgroup (tap-0 threads, before the barrier) instead of once per wave; 2: both axes' taps as
+// one packed chain (tap_axis2); 4: packed compute phase (two taps per v_pk_* instruction) for
+// regular taps; 8: for irregular taps; 16: the workgroup's mode flags reduced per wave by two
+// ballots (one LDS atomic per wave, not one pass of a loop per flagged lane: on integer
+// coordinates nearly every lane is flagged); 32: the flags computed between the gather's loads
+// and its LDS stores (in the loads' shadow), not ahead of the loads.
+constexpr int kOptWords = 1, kOptTaps2 = 2, kOptPkCompute = 4, kOptPkIrregular = 8, kOptBallotFlags = 16,
+              kOptLateFlags = 32;
+// The library runs words + packed taps + ballot flags; the packed compute phases and the late
+// flags measured no faster in the whole kernel (profiles/r09_lookup_issue.md) and stay kbench
+// variants.
+#ifdef CORR_LOOKUP_OPT  // an A/B build of the library (tools/ab_step.py)
+constexpr int kLookupOpt = CORR_LOOKUP_OPT;
+#else
+constexpr int kLookupOpt = kOptWords | kOptTaps2 | kOptBallotFlags;
+#endif
+
+// The gather's two words of a query anchored at (X0, Y0) (not far):
+// word: bits 0..4 the chunk columns inside the map (and, TIGHT, touched by the taps), 5..7 the
+// chunk column that holds the map's last cells (7: none), 8..24 the rows likewise, 26..27 y3,
+// 28..29 a; qoff: the wave-uniform byte offset.  Fully outside queries: no bits but a.
+template <int S, int QB, bool TIGHT>
+__device__ __forceinline__ void gather_words(const LookupSmem<S, QB> &sm, int qq, int X0, int Y0, int TW, int TC,
+                                             int Hl, unsigned &word, int &qoff) {
+    constexpr int WIN = LookupSmem<S, QB>::WIN, NTC = LookupSmem<S, QB>::NTC;
+    const int sX = X0 >> 2, a = X0 & 3, sY = Y0 >> 2, y3 = Y0 & 3;
+    int xhi = TW - sX, yhi = Hl - Y0;
+    if (TIGHT) {
+        const float fx0 = sm.fx[0][qq], fxl = sm.fx[1][qq], fy0 = sm.ty[0][0][qq], fyl = sm.ty[0][S - 1][qq];
+        if (window_covers<S>(fx0, fxl, fy0, fyl)) {  // chunk columns start at X0 & ~3
+            xhi = min(xhi, ((int)(fxl - fx0) + 2 + a + 3) >> 2);
+            yhi = min(yhi, (int)(fyl - fy0) + 2);
+        } else {
+            xhi = min(xhi, (WIN + a + 3) >> 2);
+        }
+    }
+    const int xlo = min(max(-sX, 0), NTC), ylo = min(max(-Y0, 0), WIN);
+    xhi = min(max(xhi, xlo), NTC), yhi = min(max(yhi, ylo), WIN);
+    const unsigned cols = ((1u << (xhi - xlo)) - 1u) << xlo, rows = ((1u << (yhi - ylo)) - 1u) << ylo;
+    const unsigned tl = (unsigned)(TW - 1 - sX) < (unsigned)NTC ? (unsigned)(TW - 1 - sX) : 7u;
+    word = (unsigned)a << 28;
+    if (cols != 0 && rows != 0) {
+        word |= cols | (tl << 5) | (rows << 8) | ((unsigned)y3 << 26);
+        qoff = (int)(64u * (unsigned)(sY * TC + sX) + 16u * (unsigned)y3);
+    }
+}
 
 // Forward gather from the tiled maps (corr_common.h): one wave per query at a time, lane =
 // (window row rr, tile column tc): one 16-B load of the tile row holding cells (anchor_y + rr,
@@ -82,15 +157,19 @@ struct LookupSmem {
 // window (unconditional: out-of-window cells go to the row's spare columns).  All of a thread's
 // loads are issued before any LDS store, so the gather costs one memory round trip.  What
 // depends only on the lane is computed once per level, what depends only on the query once per
-// wave (all of its queries at once, lane k for query k, then readlane); per query and lane there
-// remain two selects, a mask test, the buffer load and the LDS stores (profiles/r07_lookup_gather.md:
-// 383 -> 309 VALU instructions per wave at DSEC).  TIGHT: only the rows / 16-B chunks the query's taps can touch (anchor ..
+// workgroup (PRE) or per wave (all of its queries at once, lane k for query k), then readlane; per
+// query and lane there remain two selects, a mask test, the buffer load and the LDS stores
+// (profiles/r07_lookup_gather.md: 383 -> 309 VALU instructions per wave at DSEC;
+// profiles/r09_lookup_issue.md for PRE).  TIGHT: only the rows / 16-B chunks the query's taps can touch (anchor ..
 // floor(last tap) + 1 on each axis: floors are monotone in the tap index) are loaded — a regular
 // window is 10 x 10 of the 11 x 11 neighbourhood; uncovered and far queries load all of it.  The
 // cells not loaded are written as zeros and never read.  NOLOAD: ablation (tools/kbench_lookup.hip).
-template <int S, int QB, int NT, bool NOLOAD = false, bool TIGHT = false>
+// PRE: the per-query words were left in sm.gw / sm.go by the tap-0 threads (kOptWords; lookup_block_v)
+// and each wave only reads its queries' two.
+// mid(): the caller's work that needs no window, run once the loads are issued.
+template <int S, int QB, int NT, bool NOLOAD = false, bool TIGHT = false, bool PRE = false, class Mid>
 __device__ __forceinline__ void gather_window_tiled(LookupSmem<S, QB> &sm, const float *P, size_t qbase,
-                                                    unsigned mapsz, int n0, int N, int Wl, int Hl, int tid) {
+                                                    unsigned mapsz, int n0, int N, int Wl, int Hl, int tid, Mid mid) {
     using SM = LookupSmem<S, QB>;
     constexpr int WIN = SM::WIN, NTC = SM::NTC, WW = SM::WW, WQ = SM::WQ;
     constexpr int LPQ = NTC * WIN;           // lanes per query
@@ -128,37 +207,16 @@ __device__ __forceinline__ void gather_window_tiled(LookupSmem<S, QB> &sm, const
         lrow[v] = &sm.win[wu * WQ + rr * WW + 4 * tc + 3];
     }
     // ---- per query, computed for all of the wave's queries at once: lane k = query wu + NW k ----
-    // word: bits 0..4 the chunk columns inside the map (and, TIGHT, touched by the taps), 5..7 the
-    // chunk column that holds the map's last cells (7: none), 8..24 the rows likewise, 26..27 y3,
-    // 28..29 a; qoff: the wave-uniform byte offset.  Far, dead and fully outside queries: no bits.
+    // Far, dead and fully outside queries: no bits (gather_words).
     unsigned word = 0;
     int qoff = 0;
     {
         const int qq = wu + NW * lane;
-        if (lane < QPW && qq < QB && n0 + qq < N) {
+        if (PRE) {
+            if (lane < QPW && qq < QB) word = sm.gw[qq], qoff = sm.go[qq];
+        } else if (lane < QPW && qq < QB && n0 + qq < N) {
             const int X0 = sm.ax[qq], Y0 = sm.ay[qq];
-            if (X0 != kFarAnchor && Y0 != kFarAnchor) {
-                const int sX = X0 >> 2, a = X0 & 3, sY = Y0 >> 2, y3 = Y0 & 3;
-                int xhi = TW - sX, yhi = Hl - Y0;
-                if (TIGHT) {
-                    const float fx0 = sm.fx[0][qq], fxl = sm.fx[1][qq], fy0 = sm.ty[0][0][qq], fyl = sm.ty[0][S - 1][qq];
-                    if (window_covers<S>(fx0, fxl, fy0, fyl)) {  // chunk columns start at X0 & ~3
-                        xhi = min(xhi, ((int)(fxl - fx0) + 2 + a + 3) >> 2);
-                        yhi = min(yhi, (int)(fyl - fy0) + 2);
-                    } else {
-                        xhi = min(xhi, (WIN + a + 3) >> 2);
-                    }
-                }
-                const int xlo = min(max(-sX, 0), NTC), ylo = min(max(-Y0, 0), WIN);
-                xhi = min(max(xhi, xlo), NTC), yhi = min(max(yhi, ylo), WIN);
-                const unsigned cols = ((1u << (xhi - xlo)) - 1u) << xlo, rows = ((1u << (yhi - ylo)) - 1u) << ylo;
-                const unsigned tl = (unsigned)(TW - 1 - sX) < (unsigned)NTC ? (unsigned)(TW - 1 - sX) : 7u;
-                word = (unsigned)a << 28;
-                if (cols != 0 && rows != 0) {
-                    word |= cols | (tl << 5) | (rows << 8) | ((unsigned)y3 << 26);
-                    qoff = (int)(64u * (unsigned)(sY * TC + sX) + 16u * (unsigned)y3);
-                }
-            }
+            if (X0 != kFarAnchor && Y0 != kFarAnchor) gather_words<S, QB, TIGHT>(sm, qq, X0, Y0, TW, TC, Hl, word, qoff);
         }
     }
     // ---- loads: all of a wave's queries before any LDS store ----
@@ -194,6 +252,7 @@ __device__ __forceinline__ void gather_window_tiled(LookupSmem<S, QB> &sm, const
             vals[k][v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
         }
     }
+    mid();
     // ---- LDS stores ----
     auto store_all = [&](auto rag) {
         constexpr bool RAGGED = decltype(rag)::value;
@@ -231,7 +290,7 @@ constexpr int lookup_threads(int S, int QB) { return (QB * S + 63) / 64 * 64; }
 // (global NCHW stores), lookup_conv_kernel (LDS tile feeding the fused 1x1 convolution) and
 // lookup_conv_bwd_dw_kernel.  The lookup of one block with its coords already loaded (cxv, cyv:
 // this thread's query; 0 for threads without one).
-template <int S, int QB, int NT, int ABL, class Emit, bool TIGHT = false>
+template <int S, int QB, int NT, int ABL, class Emit, bool TIGHT = false, int OPT = kLookupOpt>
 __device__ __forceinline__ void lookup_block_v(LookupSmem<S, QB> &sm, const float *__restrict__ P, float cxv,
                                                float cyv, int b, int n0, int N, int H, int W, int l, int tid,
                                                Emit emit) {
@@ -252,34 +311,64 @@ __device__ __forceinline__ void lookup_block_v(LookupSmem<S, QB> &sm, const floa
 
     // ---- 1. taps ----
     if (tid == 0) sm.flags = 0;
-    const Axis tx = tap_axis(cxv, inv_scale, i, R, Wl, recip_rn((float)(Wl - 1)));
-    const Axis ty = tap_axis(cyv, inv_scale, i, R, Hl, recip_rn((float)(Hl - 1)));
+    Axis tx, ty;
+    if constexpr ((OPT & kOptTaps2) != 0) {
+        const pk2 den = {(float)(Wl - 1), (float)(Hl - 1)};
+        const Axis2 t2 = tap_axis2(cxv, cyv, inv_scale, i, R, den, recip_rn2(den));
+        tx = t2.x(), ty = t2.y();
+    } else {
+        tx = tap_axis(cxv, inv_scale, i, R, Wl, recip_rn((float)(Wl - 1)));
+        ty = tap_axis(cyv, inv_scale, i, R, Hl, recip_rn((float)(Hl - 1)));
+    }
+    // TIGHT's extents need the last tap's floors, which other waves produce: per wave, after the barrier
+    constexpr bool PRE = (OPT & kOptWords) != 0 && !TIGHT;
     if (act) {
         sm.ty[0][i][q] = ty.f;
         sm.ty[1][i][q] = ty.lo;
         sm.ty[2][i][q] = ty.hi;
         if (i == 0) {
-            sm.ax[q] = anchor_of(tx.f);
-            sm.ay[q] = anchor_of(ty.f);
+            const int X0 = anchor_of(tx.f), Y0 = anchor_of(ty.f);
+            sm.ax[q] = X0;
+            sm.ay[q] = Y0;
             sm.fx[0][q] = tx.f;
+            if constexpr (PRE) {  // the tap-0 threads hold all the gather's words need: once per workgroup
+                unsigned word = 0;
+                int qoff = 0;
+                if (n < N && X0 != kFarAnchor && Y0 != kFarAnchor)
+                    gather_words<S, QB, false>(sm, q, X0, Y0, map_tiles(Wl), TC, Hl, word, qoff);
+                sm.gw[q] = word;
+                sm.go[q] = qoff;
+            }
         }
         if (i == S - 1) sm.fx[1][q] = tx.f;
     }
     __syncthreads();
     // Workgroup-uniform mode: bit 0 = some corner lies outside its neighbourhood (slow path),
     // bit 1 = some query's taps are not regular (floor(tap t) != floor(tap 0) + t).
-    if (act) {
-        const int ax0 = sm.ax[q], ay0 = sm.ay[q];
-        const bool far = ax0 == kFarAnchor || ay0 == kFarAnchor;
-        const bool reg = far || (tx.f == (float)(ax0 + i) && ty.f == (float)(ay0 + i));
-        int f = reg ? 0 : 2;
-        // covering is a property of the query: its tap-0 threads test it (one wave, not all)
-        if (i == 0 && !window_covers<S>(sm.fx[0][q], sm.fx[1][q], sm.ty[0][0][q], sm.ty[0][S - 1][q])) f |= 1;
-        if (f) atomicOr(&sm.flags, f);
-    }
+    constexpr bool LATE = (OPT & kOptLateFlags) != 0, BALLOT = (OPT & kOptBallotFlags) != 0;
+    auto set_flags = [&]() {
+        int f = 0;
+        if (act) {
+            const int ax0 = sm.ax[q], ay0 = sm.ay[q];
+            const bool far = ax0 == kFarAnchor || ay0 == kFarAnchor;
+            const bool reg = far || (tx.f == (float)(ax0 + i) && ty.f == (float)(ay0 + i));
+            f = reg ? 0 : 2;
+            // covering is a property of the query: its tap-0 threads test it (one wave, not all)
+            if (i == 0 && !window_covers<S>(sm.fx[0][q], sm.fx[1][q], sm.ty[0][0][q], sm.ty[0][S - 1][q])) f |= 1;
+            if (!BALLOT && f) atomicOr(&sm.flags, f);
+        }
+        if (BALLOT) {  // every thread of the wave is here: the wave's flags, then one atomic
+            const int wf = (__builtin_amdgcn_ballot_w64((f & 1) != 0) != 0 ? 1 : 0) |
+                           (__builtin_amdgcn_ballot_w64((f & 2) != 0) != 0 ? 2 : 0);
+            if (wf != 0 && (tid & 63) == 0) atomicOr(&sm.flags, wf);
+        }
+    };
+    if (!LATE) set_flags();
 
     // ---- 2. neighbourhoods -> LDS ----
-    gather_window_tiled<S, QB, NT, (ABL & 1) != 0, TIGHT>(sm, P, qbase, mapsz, n0, N, Wl, Hl, tid);
+    gather_window_tiled<S, QB, NT, (ABL & 1) != 0, TIGHT, PRE>(sm, P, qbase, mapsz, n0, N, Wl, Hl, tid, [&]() {
+        if (LATE) set_flags();
+    });
     __syncthreads();
     const int mode = sm.flags;
     if (!act) return;
@@ -288,7 +377,59 @@ __device__ __forceinline__ void lookup_block_v(LookupSmem<S, QB> &sm, const floa
     const int ax = sm.ax[q], ay = sm.ay[q];
     const float *wq = &sm.win[q * WQ + 3];
     const float x0 = tx.f, ex = tx.lo, wx = tx.hi;
-    if (mode == 0) {
+    constexpr int HP = S / 2;  // S = 2 HP + 1
+    if (mode == 0 && (OPT & kOptPkCompute) != 0 && HP > 0) {
+        // regular taps, two per instruction: taps j and j + HP (j < HP) run as one packed chain
+        // (v_pk_mul_f32 / v_pk_fma_f32: per component the scalar chain's operations in its order).
+        // Tap j reads rows j, j + 1 and tap j + HP rows j + HP, j + HP + 1, so with the row pairs
+        // p[k] = (row k, row k + HP), k = 0 .. HP, chain j takes p[j] and p[j + 1]: every row is
+        // read once, both halves of a pair in one LDS instruction, and no pair is built by moves.
+        // The last tap (S - 1 = 2 HP: rows 2 HP = p[HP]'s high half, and S) stays scalar.
+        // lds_pair: one ds_read2_b32 per pair where its offsets fit (left to itself the compiler
+        // pairs neighbouring columns instead and then builds every operand pair with two moves).
+        const float *col = wq + i;
+        constexpr bool RD2 = S * WW + 1 <= 255 && (S - 2) * QB <= 255;
+        pk2 p0[HP + 1], p1[HP + 1], eys[HP + 1], nys[HP + 1];
+        const float *ty1 = &sm.ty[1][0][q], *ty2 = &sm.ty[2][0][q];
+        static_for<0, HP + 1>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            p0[k] = lds_pair<RD2, k * WW, (k + HP) * WW>(col);
+            p1[k] = lds_pair<RD2, k * WW + 1, (k + HP) * WW + 1>(col);
+            if constexpr (k < HP) {
+                eys[k] = lds_pair<RD2, k * QB, (k + HP) * QB>(ty1);
+                nys[k] = lds_pair<RD2, k * QB, (k + HP) * QB>(ty2);
+            }
+        });
+        float l0 = col[S * WW], l1 = col[S * WW + 1], eyl = sm.ty[1][S - 1][q], nyl = sm.ty[2][S - 1][q];
+        if constexpr (RD2) {
+            // the compiler does not count lds_pair's reads: wait for them here, and order every use
+            // of a pair behind the wait
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int k = 0; k <= HP; ++k) asm volatile("" : "+v"(p0[k]), "+v"(p1[k]));
+#pragma unroll
+            for (int j = 0; j < HP; ++j) asm volatile("" : "+v"(eys[j]), "+v"(nys[j]));
+            asm volatile("" : "+v"(l0), "+v"(l1), "+v"(eyl), "+v"(nyl));  // (keeps the last tap's reads up here)
+        }
+#pragma unroll
+        for (int j = 0; j < HP; ++j) {
+            const pk2 ey = eys[j], ny = nys[j];
+            pk2 acc = p0[j] * (ey * ex);
+            acc = __builtin_elementwise_fma(p1[j], ey * wx, acc);
+            acc = __builtin_elementwise_fma(p0[j + 1], ny * ex, acc);
+            acc = __builtin_elementwise_fma(p1[j + 1], ny * wx, acc);
+            if (qok && (!(ABL & 2) || acc.x == 1234.5f)) emit(j, acc.x);
+            if (qok && (!(ABL & 2) || acc.y == 1234.5f)) emit(j + HP, acc.y);
+        }
+        {
+            const float ey = eyl, ny = nyl;
+            float acc = __fmul_rn(p0[HP].y, __fmul_rn(ey, ex));
+            acc = __builtin_fmaf(p1[HP].y, __fmul_rn(ey, wx), acc);
+            acc = __builtin_fmaf(l0, __fmul_rn(ny, ex), acc);
+            acc = __builtin_fmaf(l1, __fmul_rn(ny, wx), acc);
+            if (qok && (!(ABL & 2) || acc == 1234.5f)) emit(S - 1, acc);
+        }
+    } else if (mode == 0) {
         // regular taps: tap (i, j) has corners at neighbourhood column i, i+1 and rows j, j+1,
         // so the S+1 rows of the column pair are read once and shared by consecutive taps
         // (far queries read an all-zero neighbourhood: their taps have no in-map corner).
@@ -313,8 +454,22 @@ __device__ __forceinline__ void lookup_block_v(LookupSmem<S, QB> &sm, const floa
         const bool far = (ax == kFarAnchor) || (ay == kFarAnchor);
         const int cx = far ? 0 : (int)x0 - ax;
         const float *col = wq + cx;
+        // (kOptPkIrregular) taps j and j + 1 as one packed chain, the weights and the chain packed as
+        // above; the corners' rows differ per tap, so their pairs are built with moves
+        constexpr int SP = (OPT & kOptPkIrregular) != 0 ? (S & ~1) : 0;
 #pragma unroll
-        for (int j = 0; j < S; ++j) {
+        for (int j = 0; j < SP; j += 2) {
+            const pk2 y0 = {sm.ty[0][j][q], sm.ty[0][j + 1][q]}, ey = {sm.ty[1][j][q], sm.ty[1][j + 1][q]},
+                      ny = {sm.ty[2][j][q], sm.ty[2][j + 1][q]};
+            const float *ca = col + (far ? 0 : (int)y0.x - ay) * WW, *cb = col + (far ? 0 : (int)y0.y - ay) * WW;
+            pk2 acc = pk2{ca[0], cb[0]} * (ey * ex);
+            acc = __builtin_elementwise_fma(pk2{ca[1], cb[1]}, ey * wx, acc);
+            acc = __builtin_elementwise_fma(pk2{ca[WW], cb[WW]}, ny * ex, acc);
+            acc = __builtin_elementwise_fma(pk2{ca[WW + 1], cb[WW + 1]}, ny * wx, acc);
+            if (qok) emit(j, acc.x), emit(j + 1, acc.y);
+        }
+#pragma unroll
+        for (int j = SP; j < S; ++j) {
             const float y0 = sm.ty[0][j][q], ey = sm.ty[1][j][q], ny = sm.ty[2][j][q];
             const int cy = far ? 0 : (int)y0 - ay;
             const float *c = col + cy * WW;
@@ -346,7 +501,7 @@ __device__ __forceinline__ void lookup_block_v(LookupSmem<S, QB> &sm, const floa
     }
 }
 
-template <int S, int QB, int NT, int ABL, bool TIGHT = false, class Emit>
+template <int S, int QB, int NT, int ABL, bool TIGHT = false, int OPT = kLookupOpt, class Emit>
 __device__ __forceinline__ void lookup_block(LookupSmem<S, QB> &sm, const float *__restrict__ P,
                                              const float *__restrict__ coords, int b, int n0, int N,
                                              int H, int W, int l, int tid, Emit emit) {
@@ -354,10 +509,10 @@ __device__ __forceinline__ void lookup_block(LookupSmem<S, QB> &sm, const float 
     const bool qok = tid / QB < S && n < N;
     const float cxv = (ABL & 4) ? (float)(n % W) : qok ? coords[((size_t)b * 2 + 0) * N + n] : 0.0f;
     const float cyv = (ABL & 4) ? (float)(n / W) : qok ? coords[((size_t)b * 2 + 1) * N + n] : 0.0f;
-    lookup_block_v<S, QB, NT, ABL, Emit, TIGHT>(sm, P, cxv, cyv, b, n0, N, H, W, l, tid, emit);
+    lookup_block_v<S, QB, NT, ABL, Emit, TIGHT, OPT>(sm, P, cxv, cyv, b, n0, N, H, W, l, tid, emit);
 }
 
-template <int S, int QB, int ABL = 0, bool TIGHT = false>
+template <int S, int QB, int ABL = 0, bool TIGHT = false, int OPT = kLookupOpt>
 __global__ __launch_bounds__(lookup_threads(S, QB)) void lookup_kernel(
     ConstLevelPtrs pyr, const float *__restrict__ coords, int B, int NQ, int H, int W, int L,
     float *__restrict__ out) {
@@ -373,7 +528,7 @@ __global__ __launch_bounds__(lookup_threads(S, QB)) void lookup_kernel(
     // stores then measured slower: DSEC 5.22 -> 5.31 us, train 9.68 -> 9.84; a 32-bit thread offset
     // into the 64-bit pointer alone is a wash; profiles/r07_lookup_gather.md)
     float *o = out + (((size_t)b * L + l) * K + (size_t)i * S) * N + n;
-    lookup_block<S, QB, NT, ABL, TIGHT>(sm, pyr.p[l], coords, b, n0, N, H, W, l, (int)threadIdx.x, [&](int j, float acc) {
+    lookup_block<S, QB, NT, ABL, TIGHT, OPT>(sm, pyr.p[l], coords, b, n0, N, H, W, l, (int)threadIdx.x, [&](int j, float acc) {
         // non-temporal: the output streams past L2 (nothing in this kernel re-reads it), so the
         // kernel's end has no dirty lines of it to write back (DSEC 5.8 -> 5.4 us, train 12.2 ->
         // 11.4 us, same bits; profiles/r04q_kbench_lookup_nt.txt)
@@ -1873,7 +2028,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float *__restrict__
     }
 }
 
-template <int S, int QB>
+template <int S, int QB, int OPT = kLookupOpt>
 hipError_t launch_lookup_qb(const ConstLevelPtrs &pyr, const float *coords, int B, int NQ, int H, int W, int L,
                             float *out, hipStream_t s) {
     // TIGHT (only the window rows / 16-B chunks the query's taps touch) pays once the grid is
@@ -1882,15 +2037,15 @@ hipError_t launch_lookup_qb(const ConstLevelPtrs &pyr, const float *coords, int 
     // 15.9 -> 15.5, MVSEC 36x44 B16 18.6 -> 18.5; DSEC 5.6 -> 6.1, train B8 10.4 -> 10.6)
     const int nqb = (NQ + QB - 1) / QB;
     if ((long)B * NQ >= 18000)
-        hipLaunchKernelGGL((lookup_kernel<S, QB, 0, true>), dim3(nqb * B, L), dim3(lookup_threads(S, QB)), 0, s,
+        hipLaunchKernelGGL((lookup_kernel<S, QB, 0, true, OPT>), dim3(nqb * B, L), dim3(lookup_threads(S, QB)), 0, s,
                            pyr, coords, B, NQ, H, W, L, out);
     else
-        hipLaunchKernelGGL((lookup_kernel<S, QB>), dim3(nqb * B, L), dim3(lookup_threads(S, QB)), 0, s, pyr, coords,
+        hipLaunchKernelGGL((lookup_kernel<S, QB, 0, false, OPT>), dim3(nqb * B, L), dim3(lookup_threads(S, QB)), 0, s, pyr, coords,
                            B, NQ, H, W, L, out);
     return hipGetLastError();
 }
 
-template <int S>
+template <int S, int OPT = kLookupOpt>
 hipError_t launch_lookup_s(const ConstLevelPtrs &pyr, const float *coords, int B, int NQ, int H,
                            int W, int L, float *out, hipStream_t s) {
     // queries per workgroup: 32; 16 for r = 4 on maps of <= 2048 cells with >= 20,000 queries in
@@ -1899,8 +2054,8 @@ hipError_t launch_lookup_s(const ConstLevelPtrs &pyr, const float *coords, int B
     // QB 16 / 32 = MVSEC 36x44 B16 19.0 / 19.6 us, B12 36x48 16.1 / 16.1; train B8 12.0 / 11.7,
     // MVSEC crop 32x32 B16 12.3 / 11.3, DSEC 5.5 / 5.4, 1280x960 22.6 / 22.1; with the tiled
     // pyramid, profiles/r05m_kbench_lookup.txt: MVSEC 18.6 / 19.2, B12 15.9 / 15.7, train 10.3 / 10.2)
-    if (S == 9 && H * W <= 2048 && (long)B * NQ >= 20000) return launch_lookup_qb<S, 16>(pyr, coords, B, NQ, H, W, L, out, s);
-    return launch_lookup_qb<S, 32>(pyr, coords, B, NQ, H, W, L, out, s);
+    if (S == 9 && H * W <= 2048 && (long)B * NQ >= 20000) return launch_lookup_qb<S, 16, OPT>(pyr, coords, B, NQ, H, W, L, out, s);
+    return launch_lookup_qb<S, 32, OPT>(pyr, coords, B, NQ, H, W, L, out, s);
 }
 
 template <int S>
