@@ -21,7 +21,7 @@
 // epilogue (the build's bf16x6 scheme): no narrower than an fp32 GEMM.
 //
 // Row maxima (f16x3 only): F1 / F2 from rowmax2_kernel; dC's row and column maxima from the fused backward
-// (corr_lookup.hip) or, for a caller-supplied dC, from absmax_kernel (unsigned atomicMax on the
+// (corr_lookup_fold.hip) or, for a caller-supplied dC, from absmax_kernel (unsigned atomicMax on the
 // bits of non-negative floats: exact and order free).  Also here: the pool-backward fold with
 // dC's maxima (pool_fold_max_kernel) and the column-maxima reduce of the fused backward.
 #include <algorithm>

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/corr_mi355x.h"
 
@@ -81,6 +82,23 @@ __device__ __forceinline__ float nanfix_flat(const NanFix &f, size_t e) {
     const size_t per = (size_t)f.NI * f.NJ;
     const size_t r = e % per;
     return nanfix_dot(f, (int)(e / per), (int)(r / f.NJ), (int)(r % f.NJ));
+}
+
+// The lookups are compiled per window size S = 2 radius + 1: f(std::integral_constant<int, S>{})
+// for radius 0..7, hipErrorInvalidValue outside.
+template <class F>
+hipError_t dispatch_radius(int radius, F f) {
+    switch (radius) {
+        case 0: return f(std::integral_constant<int, 1>{});
+        case 1: return f(std::integral_constant<int, 3>{});
+        case 2: return f(std::integral_constant<int, 5>{});
+        case 3: return f(std::integral_constant<int, 7>{});
+        case 4: return f(std::integral_constant<int, 9>{});
+        case 5: return f(std::integral_constant<int, 11>{});
+        case 6: return f(std::integral_constant<int, 13>{});
+        case 7: return f(std::integral_constant<int, 15>{});
+        default: return hipErrorInvalidValue;
+    }
 }
 
 // Set the thread-local error and return `code`.

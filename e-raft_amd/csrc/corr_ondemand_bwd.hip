@@ -18,7 +18,7 @@
 // 1. ondemand_bwd_window_kernel — a wave owns a query (all its levels, in order).  The K upstream
 //    values are scattered into the query's own (S+2)^2 cell block anchored at the floor of tap 0,
 //    each tap taking its floor from its own coordinate (floors are NOT assumed regular: on and near
-//    the integer grid single floors move by one cell, see lookup_bwd_kernel in corr_lookup.hip).
+//    the integer grid single floors move by one cell, see lookup_bwd_kernel in corr_lookup_bwd.hip).
 //    Lane = cell: the cell sums its contributions x-tap outer, y-tap inner (at most one corner of a
 //    tap lands on a given cell), i.e. the sequential scatter's order restricted to that cell.  The
 //    block and its origin go to the workspace (origin = kFarAnchor: nothing here), and

@@ -1,6 +1,7 @@
-// The lookup's tap arithmetic, shared by corr_lookup.hip (lookups of the materialised pyramid)
-// and corr_ondemand.hip (lookups straight from the feature maps): one copy, so both round every
-// tap coordinate, floor and corner weight identically.
+// The lookup's tap arithmetic, shared by the lookups of the materialised pyramid
+// (corr_lookup_block.h forward; corr_lookup_bwd.hip and corr_lookup_fold.hip backward) and
+// corr_ondemand*.hip (lookups straight from the feature maps): one copy, so all round every tap
+// coordinate, floor and corner weight identically.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,6 +79,13 @@ __device__ __forceinline__ int anchor_of(float f) {
 
 __device__ __forceinline__ bool in_map(float xf, float yf, int Wl, int Hl) {
     return xf >= 0.0f && xf < (float)Wl && yf >= 0.0f && yf < (float)Hl;
+}
+
+// True when every in-map corner of the query's taps lies inside its (S+2)^2 neighbourhood.
+template <int S>
+__device__ __forceinline__ bool window_covers(float fx0, float fxl, float fy0, float fyl) {
+    if (anchor_of(fx0) == kFarAnchor || anchor_of(fy0) == kFarAnchor) return true;
+    return (fxl - fx0) <= (float)S && (fyl - fy0) <= (float)S;
 }
 
 }  // namespace corr

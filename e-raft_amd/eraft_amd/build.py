@@ -6,6 +6,7 @@ plain C-ABI of include/corr_mi355x.h, loaded with ctypes.
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 
@@ -14,10 +15,12 @@ SRC = os.path.join(os.path.dirname(PKG), "csrc")
 OUT_DIR = os.path.join(PKG, "_build")
 SO_NAME = "libcorr_mi355x.so"
 SO_PATH = os.path.join(OUT_DIR, SO_NAME)
-SOURCES = ["corr_build.hip", "corr_build_split.hip", "corr_build_bf16.hip", "corr_lookup.hip", "corr_ondemand.hip", "corr_ondemand_bwd.hip", "corr_bwd.hip", "corr_bwd_split.hip", "corr_splat.hip",
-           "corr_upsample.hip", "corr_voxel.hip", "corr_gru.hip",
+SOURCES = ["corr_build.hip", "corr_build_split.hip", "corr_build_bf16.hip", "corr_lookup.hip", "corr_lookup_conv.hip",
+           "corr_lookup_bwd.hip", "corr_lookup_fold.hip", "corr_ondemand.hip", "corr_ondemand_bwd.hip", "corr_bwd.hip",
+           "corr_bwd_split.hip", "corr_splat.hip", "corr_upsample.hip", "corr_voxel.hip", "corr_gru.hip",
            "corr_api.cpp"]
-HEADERS = ["corr_common.h", "corr_build_common.h", "corr_div.h", "corr_taps.h", "corr_ondemand_common.h", os.path.join("..", "..", "include", "corr_mi355x.h")]
+# every header counts as a dependency of every translation unit (paths relative to csrc/)
+HEADERS = sorted(glob.glob("*.h", root_dir=SRC)) + [os.path.join("..", "..", "include", "corr_mi355x.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the lookup / pool arithmetic is specified op-by-op (each fp32 op rounds

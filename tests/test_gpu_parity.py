@@ -351,7 +351,7 @@ def test_gpu_pyramid_and_lookup_vs_oracle(B, D, H, W, L, r, algo, monkeypatch):
 @pytest.mark.parametrize("B,H,W", [(1, 120, 160), (2, 90, 104)])
 def test_lookup_tight_gather_vs_oracle(B, H, W):
     """>= 18,000 queries: the lookup gathers only the window rows / 16-B chunks its taps touch
-    (corr_lookup.hip launch_lookup_qb, TIGHT).  Bit-exact against the oracle on the exported
+    (corr_lookup.hip launch_lookup_qb; TIGHT in corr_lookup_block.h).  Bit-exact against the oracle on the exported
     pyramid for random flows, the integer grid (every tap on a cell: the window's extra row and
     column unused), the special coordinates (borders, far outside, half pixels) and NaN / inf /
     huge coordinates sprinkled over the map."""

@@ -1,4 +1,4 @@
-"""The lookup's window gather (corr_lookup.hip gather_window_tiled) at the smallest shapes where
+"""The lookup's window gather (corr_lookup_block.h gather_window_tiled) at the smallest shapes where
 each of its paths can go wrong: windows larger than the map, a 1x1 level, ragged tile columns,
 partial last blocks, every window size (more than one load per lane and query from r = 6), the
 TIGHT gather (>= 18,000 queries), 16 queries per workgroup, and a row slab of queries.  Every

@@ -1,4 +1,4 @@
-"""The lookup kernel's instruction-count changes (corr_lookup.hip: the gather's per-query words
+"""The lookup kernel's instruction-count changes (corr_lookup_block.h: the gather's per-query words
 computed once per workgroup, both axes' taps as one packed chain, the workgroup's mode flags
 reduced by ballots) at the smallest shapes where each can go wrong: S = 1, 3, 9 and 15 (more
 than one load per lane and query), windows larger than the maps, a 1x1 level, ragged tile columns,

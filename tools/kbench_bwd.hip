@@ -1,4 +1,4 @@
-// kbench_bwd.hip — where lookup_bwd_fold_kernel (corr_lookup.hip) spends its time at the train
+// kbench_bwd.hip — where lookup_bwd_fold_kernel (corr_lookup_fold.hip) spends its time at the train
 // shape (B8, 36x48, r4, L4, 12 lookups): the full kernel against probes that drop the lookup
 // loop, the fold (dC + maxima), or the LDS zero-init (timing only; wrong results).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 -ffp-contract=off -o tools/_build/kbench_bwd tools/kbench_bwd.hip
@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "../e-raft_amd/csrc/corr_lookup.hip"
+#include "../e-raft_amd/csrc/corr_lookup_fold.hip"
 
 using namespace corr;
 

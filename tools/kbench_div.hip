@@ -1,5 +1,5 @@
 // kbench_div.hip — exhaustive check of the reciprocal-and-correct division the lookup's tap
-// arithmetic can use in place of __fdiv_rn (corr_lookup.hip tap_axis: 2x / (size - 1)):
+// arithmetic can use in place of __fdiv_rn (corr_taps.h tap_axis: 2x / (size - 1)):
 //   y = RN(1 / d) (once per level), q = RN(a y), r = fma(-q, d, a) (exact), q' = fma(r, y, q)
 // (Markstein's correction), with y from v_rcp_f32 and one Newton step (recip_rn).  First every
 // d = 1 .. 2^20 checks recip_rn(d) == __fdiv_rn(1, d); then for every float bit pattern a and

@@ -3,7 +3,8 @@
 // split-K reduce, for several split counts, register-staged vs LDS-DMA operand ring (HIP events
 // around back-to-back launches; results against the register-staged plan, which must match bitwise).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 -ffp-contract=off -o tools/_build/kbench_gemm tools/kbench_gemm.hip \
-//         e-raft_amd/csrc/corr_bwd.hip e-raft_amd/csrc/corr_build.hip e-raft_amd/csrc/corr_lookup.hip
+//         e-raft_amd/csrc/corr_bwd.hip e-raft_amd/csrc/corr_build.hip e-raft_amd/csrc/corr_lookup_bwd.hip \
+//         e-raft_amd/csrc/corr_lookup_fold.hip
 #include <algorithm>
 #include <cstring>
 #include <cstdio>

@@ -80,22 +80,6 @@ static hipError_t launch_qb(const ConstLevelPtrs &pyr, const float *coords, int 
     return hipGetLastError();
 }
 
-// The instruction-count switches (corr_lookup.hip kOpt*: 0 = the forms they replace) under the
-// production rule for QB / TIGHT, on the random, integer-grid and no-load-no-store inputs.
-template <int OPT>
-static void add_opt_variants(std::vector<Variant> &vs, const ConstLevelPtrs &lp, const float *coords,
-                             const float *coords_g, int B, int H, int W) {
-    const std::string n = "opt" + std::to_string(OPT);
-    vs.push_back({n + " prod", [=](float *o) { return launch_lookup_s<9, OPT>(lp, coords, B, H * W, H, W, 4, o, 0); }, {}});
-    vs.push_back({n + " prod grid (integer)", [=](float *o) { return launch_lookup_s<9, OPT>(lp, coords_g, B, H * W, H, W, 4, o, 0); }, {}});
-    vs.push_back({"abl " + n + " QB32 noload nostore", [=](float *o) {
-                      const int nqb = (H * W + 31) / 32;
-                      hipLaunchKernelGGL((lookup_kernel<9, 32, 3, false, OPT>), dim3(nqb * B, 4), dim3(lookup_threads(9, 32)), 0, 0, lp,
-                                         coords, B, H * W, H, W, 4, o);
-                      return hipGetLastError();
-                  }, {}});
-}
-
 int main(int argc, char **argv) {
     const int rounds = argc > 1 ? atoi(argv[1]) : 40;
     constexpr int PER = 12;  // one frame pair's worth of lookups per sample
@@ -146,17 +130,6 @@ int main(int argc, char **argv) {
         vs.push_back({"abl QB32 none (taps only)", [=](float *o) { return launch_qb<32, 7>(lp, coords, B, H, W, o); }, {}});
         vs.push_back({"QB16 cached-stores", [=](float *o) { return launch_qb<16, 8>(lp, coords, B, H, W, o); }, {}});
         vs.push_back({"QB32 cached-stores", [=](float *o) { return launch_qb<32, 8>(lp, coords, B, H, W, o); }, {}});
-        add_opt_variants<0>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptWords>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptTaps2>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptWords | kOptTaps2>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptBallotFlags>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptBallotFlags | kOptLateFlags>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptWords | kOptTaps2 | kOptBallotFlags>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptWords | kOptTaps2 | kOptBallotFlags | kOptLateFlags>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptPkCompute>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptWords | kOptTaps2 | kOptPkCompute>(vs, lp, coords, coords_g, B, H, W);
-        add_opt_variants<kOptWords | kOptTaps2 | kOptPkCompute | kOptPkIrregular>(vs, lp, coords, coords_g, B, H, W);
         CK(vs[0].launch(ref));
         if (argc > 3) {  // one variant (PMC passes)
             std::vector<Variant> keep;
