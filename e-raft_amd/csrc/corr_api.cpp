@@ -583,6 +583,65 @@ int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int in
                       fn);
 }
 
+static int check_conv_channels(const char *fn, int cout, int ca, int cb) {
+    if (!conv_supported(cout, ca, cb))
+        return fail(CORR_EUNSUPPORTED,
+                    "%s: built for 1 <= cout <= 1024, ca >= 32 and cb >= 0 multiples of 32, ca + cb <= 1024 "
+                    "(got cout = %d, ca = %d, cb = %d)",
+                    fn, cout, ca, cb);
+    return CORR_OK;
+}
+
+size_t corr_conv_weights_bytes(int cout, int cin) {
+    if (!conv_supported(cout, cin, 0)) return 0;
+    return conv_weights_bytes(cout, cin);
+}
+
+int corr_conv_pack_weights(const float *w, int cout, int cin, void *packed, void *stream) {
+    static const char *fn = "corr_conv_pack_weights";
+    g_err[0] = 0;
+    int rc;
+    if ((rc = check_conv_channels(fn, cout, cin, 0))) return rc;
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_conv_pack(w, cout, cin, packed, (hipStream_t)stream), fn);
+}
+
+// [p, p + n) and [q, q + m) share a byte
+static bool ranges_overlap(const void *p, long double n, const void *q, long double m) {
+    const long double a = (long double)(uintptr_t)p, b = (long double)(uintptr_t)q;
+    return a < b + m && b < a + n;
+}
+
+int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W, const void *packed,
+                      const float *bias, int cout, int relu, float *out, int out_channels, int out_offset,
+                      void *stream) {
+    static const char *fn = "corr_conv_forward";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    if ((rc = check_conv_channels(fn, cout, ca, cb))) return rc;
+    if (relu != 0 && relu != 1) return fail(CORR_EINVAL, "%s: relu must be 0 or 1 (got %d)", fn, relu);
+    if (out_offset < 0 || (long long)out_offset + cout > out_channels)
+        return fail(CORR_EINVAL, "%s: channels out_offset .. out_offset + cout - 1 must lie in [0, out_channels) "
+                                 "(got out_offset = %d, cout = %d, out_channels = %d)",
+                    fn, out_offset, cout, out_channels);
+    if ((rc = check_ptr(fn, in_a, "in_a")) || (rc = check_ptr(fn, packed, "packed")) ||
+        (rc = check_ptr(fn, out, "out")))
+        return rc;
+    if (cb > 0 && (rc = check_ptr(fn, in_b, "in_b"))) return rc;
+    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    const long double px = (long double)B * H * W * sizeof(float), ob = px * out_channels;
+    if (ob > (long double)(SIZE_MAX / 2)) return fail(CORR_EINVAL, "%s: B*out_channels*H*W too large", fn);
+    if (ranges_overlap(out, ob, in_a, px * ca) || (cb > 0 && ranges_overlap(out, ob, in_b, px * cb)))
+        return fail(CORR_EINVAL, "%s: out must not overlap in_a or in_b", fn);
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_conv_forward(in_a, ca, in_b, cb, B, H, W, packed, bias, cout, relu, out, out_channels,
+                                          out_offset, (hipStream_t)stream),
+                      fn);
+}
+
 int corr_convex_upsample(const float *flow, const float *mask, int N, int h, int w, float *out, void *stream) {
     static const char *fn = "corr_convex_upsample";
     g_err[0] = 0;

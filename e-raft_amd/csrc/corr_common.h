@@ -209,6 +209,13 @@ hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, in
 hipError_t launch_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
                                 const void *packed, const float *bz, const float *br, const float *bq, void *ws,
                                 float *h_out, hipStream_t s);
+// 3x3 convolution + bias + ReLU over two input pointers into a channel window (corr_conv.hip).
+bool conv_supported(int cout, int ca, int cb);
+size_t conv_weights_bytes(int cout, int cin);
+hipError_t launch_conv_pack(const float *w, int cout, int cin, void *packed, hipStream_t s);
+hipError_t launch_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
+                               const void *packed, const float *bias, int cout, int relu, float *out,
+                               int out_channels, int out_offset, hipStream_t s);
 size_t build_bwd_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bwd(const float *grad_c, const float *f1, int NQ, const float *f2, int B,
                             int D, int H, int W, float *df1, float *df2, float *ws, hipStream_t s);

@@ -33,7 +33,8 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_lookup_conv_bwd_workspace", "corr_lookup_conv_bwd", "corr_map_floats", "corr_pyramid_export",
            "corr_pyramid_import", "corr_ondemand_workspace", "corr_ondemand_prepare", "corr_ondemand_lookup",
            "corr_ondemand_bwd_workspace", "corr_ondemand_backward", "corr_gru_weights_bytes",
-           "corr_gru_pack_weights", "corr_gru_workspace", "corr_gru_half_step")
+           "corr_gru_pack_weights", "corr_gru_workspace", "corr_gru_half_step", "corr_conv_weights_bytes",
+           "corr_conv_pack_weights", "corr_conv_forward")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -148,7 +149,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_gru_pack_weights.argtypes = [vp, vp, vp, i, i, vp, vp]
     lib.corr_gru_workspace.argtypes, lib.corr_gru_workspace.restype = [i, i, i, i], sz
     lib.corr_gru_half_step.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp, vp]
-    for f in ("corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
+    lib.corr_conv_weights_bytes.argtypes, lib.corr_conv_weights_bytes.restype = [i, i], sz
+    lib.corr_conv_pack_weights.argtypes = [vp, i, i, vp, vp]
+    lib.corr_conv_forward.argtypes = [vp, i, vp, i, i, i, i, vp, vp, i, i, vp, i, i, vp]
+    for f in ("corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
@@ -666,4 +670,75 @@ def gru_half_step(h, x, direction, packed, bz, br, bq, workspace=None):
         _check(lib.corr_gru_half_step(hp, xp, B, hidden, x.shape[1], H, W, direction, pk, _dev(bz, "bz"),
                                       _dev(br, "br"), _dev(bq, "bq"), _dev(workspace, "workspace"),
                                       workspace.numel() * 4, out.data_ptr(), _stream(h)))
+    return out
+
+
+def conv_pack_weights(weights):
+    """corr_conv_pack_weights: one Conv2d weight [cout, cin, 3, 3], or a list of them with equal
+    cin that are stacked along cout (their convolutions then run as one launch) -> the packed
+    split (an opaque buffer)."""
+    ws = [weights] if isinstance(weights, torch.Tensor) else list(weights)
+    if not ws:
+        raise ValueError("conv_pack_weights needs at least one weight")
+    for w in ws:
+        if not isinstance(w, torch.Tensor):
+            raise TypeError("conv weights must be torch.Tensors")
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] != ws[0].shape[1]:
+            raise ValueError(f"conv weights must be [cout, cin, 3, 3] with equal cin "
+                             f"(got {[tuple(v.shape) for v in ws]})")
+    ws = [w.detach().float() for w in ws]
+    w = (ws[0] if len(ws) == 1 else torch.cat(ws, dim=0)).contiguous()
+    cout, cin = w.shape[0], w.shape[1]
+    lib = load()
+    n = lib.corr_conv_weights_bytes(cout, cin)
+    if n == 0:
+        raise CorrError(CORR_EUNSUPPORTED, f"corr_conv_weights_bytes: unsupported cout = {cout}, cin = {cin}")
+    wp = _dev(w, "w")
+    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib.corr_conv_pack_weights(wp, cout, cin, packed.data_ptr(), _stream(w)))
+    return packed
+
+
+def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0):
+    """corr_conv_forward: the 3x3 convolution (+ bias, + ReLU) of cat([in_a, in_b]) (in_b may be
+    None) with the pack of conv_pack_weights, written into channels out_offset .. + cout - 1 of
+    `out` [B, out_channels, H, W] (allocated as [B, cout, H, W] when None).  Returns `out`."""
+    ap = _dev(in_a, "in_a")
+    if in_a.dim() != 4:
+        raise ValueError(f"in_a must be [B, ca, H, W] (got {tuple(in_a.shape)})")
+    B, ca, H, W = in_a.shape
+    cb, bp = 0, None
+    if in_b is not None:
+        bp = _dev(in_b, "in_b")
+        if in_b.dim() != 4 or in_b.shape[0] != B or tuple(in_b.shape[2:]) != (H, W):
+            raise ValueError(f"in_b {tuple(in_b.shape)} does not match in_a {tuple(in_a.shape)}")
+        if in_b.device != in_a.device:
+            raise ValueError("in_a and in_b are on different devices")
+        cb = in_b.shape[1]
+    lib = load()
+    need = lib.corr_conv_weights_bytes(cout, ca + cb)
+    if need == 0:
+        raise CorrError(CORR_EUNSUPPORTED, f"corr_conv_forward: unsupported cout = {cout}, ca = {ca}, cb = {cb}")
+    pk = _dev(packed, "packed")
+    if packed.numel() * 4 < need or packed.device != in_a.device:
+        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
+                         f"{need} on {in_a.device}")
+    biasp = None
+    if bias is not None:
+        biasp = _dev(bias, "bias")
+        if bias.numel() != cout or bias.device != in_a.device:
+            raise ValueError(f"bias must hold cout = {cout} values on {in_a.device} (got {tuple(bias.shape)})")
+    if out is None:
+        if out_offset != 0:
+            raise ValueError("out_offset needs an out tensor")
+        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=in_a.device)
+    op = _dev(out, "out")
+    if (out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (H, W) or out.device != in_a.device
+            or out_offset < 0 or out_offset + cout > out.shape[1]):
+        raise ValueError(f"out {tuple(out.shape)} does not hold channels {out_offset} .. {out_offset + cout - 1} "
+                         f"of a [{B}, *, {H}, {W}] map on {in_a.device}")
+    with torch.cuda.device(in_a.device):
+        _check(lib.corr_conv_forward(ap, ca, bp, cb, B, H, W, pk, biasp, cout, int(bool(relu)), op, out.shape[1],
+                                     out_offset, _stream(in_a)))
     return out

@@ -171,6 +171,12 @@ class FlowHead(nn.Module):
 class BasicUpdateBlock(nn.Module):
     """Motion encoder + SepConvGRU + flow head + convex-upsampling mask (update.py:85-107)."""
 
+    # ERAFT_AMD_FUSE_UPDATE=1: at inference on the MI355X the block's 3x3 convolutions are
+    # corr_conv_forward launches that write into shared buffers (update.py: no cat, bias and ReLU
+    # in the kernel) instead of MIOpen convolutions and torch glue.  Default off (DESIGN §15 has
+    # the measurements); training always runs the torch code.
+    fused = os.environ.get("ERAFT_AMD_FUSE_UPDATE", "0") == "1"
+
     def __init__(self, corr_levels=4, corr_radius=4, hidden_dim=128):
         super().__init__()
         self.encoder = BasicMotionEncoder(corr_levels, corr_radius)
@@ -179,7 +185,29 @@ class BasicUpdateBlock(nn.Module):
         self.mask = nn.Sequential(nn.Conv2d(128, 256, 3, padding=1), nn.ReLU(inplace=True),
                                   nn.Conv2d(256, 64 * 9, 1))
 
+    def _fusable(self, net, inp, corr, flow, fused):
+        """update.update_block is built for fp32 GPU tensors and the reference's channel counts,
+        and has no backward."""
+        ts = (net, inp, corr, flow)
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.device == net.device for t in ts):
+            return False
+        enc = self.encoder
+        if (net.shape[1], inp.shape[1], flow.shape[1]) != (128, 128, 2) or corr.shape[1] != (256 if fused else 324):
+            return False
+        shapes = ((enc.convc1, (256, 324, 1, 1)), (enc.convc2, (192, 256, 3, 3)), (enc.convf1, (128, 2, 7, 7)),
+                  (enc.convf2, (64, 128, 3, 3)), (enc.conv, (126, 256, 3, 3)), (self.flow_head.conv1, (256, 128, 3, 3)),
+                  (self.mask[0], (256, 128, 3, 3)))
+        if any(tuple(c.weight.shape) != s or c.bias is None for c, s in shapes):
+            return False
+        ps = list(self.parameters())
+        if any(p.dtype != torch.float32 or p.device != net.device for p in ps):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in (*ts, *ps)))
+
     def forward(self, net, inp, corr, flow, fused=False):
+        if self.fused and self._fusable(net, inp, corr, flow, fused):
+            from .update import update_block
+            return update_block(self, net, inp, corr, flow, fused)
         motion = self.encoder(flow, corr, fused)
         net = self.gru(net, torch.cat([inp, motion], dim=1))
         return net, 0.25 * self.mask(net), self.flow_head(net)

@@ -504,6 +504,45 @@ int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int in
                        const void *packed, const float *bz, const float *br, const float *bq, void *workspace,
                        size_t workspace_bytes, float *h_out, void *stream);
 
+/*
+ * A 3x3 convolution (stride 1, zero padding 1) with bias and an optional ReLU, inference only
+ * (no backward): the update block's convc2, convf2, conv and the first convolutions of the flow
+ * head and the mask head (model/update.py:63-107).
+ *   out[b][out_offset + o][y][x] =
+ *       act(bias[o] + sum_c sum_ky sum_kx w[o][c][ky][kx] * in[b][c][y + ky - 1][x + kx - 1])
+ * for o < cout; act is the identity (relu = 0) or max(., 0) (relu = 1).
+ * Input: `in` is the channel-wise concatenation of in_a [B][ca][H][W] and in_b [B][cb][H][W],
+ * two pointers and no cat; the boundary ca is any multiple of 32.  in_b is ignored (may be NULL)
+ * when cb = 0.
+ * Output: out is a [B][out_channels][H][W] tensor of which only channels out_offset ..
+ * out_offset + cout - 1 are written; every other byte of it is left as it was, so a producer can
+ * write straight into the buffer its consumer reads.  out's byte range must not overlap in_a's
+ * or in_b's (a workgroup reads its neighbours' pixels).
+ * Weights: w is a contiguous Conv2d weight [cout][cin][3][3], cin = ca + cb.  It is split once per
+ * weight version by corr_conv_pack_weights into a corr_conv_weights_bytes(cout, cin) buffer (16-B
+ * aligned, opaque; 0 for unsupported sizes).  Several convolutions over the same input run as one
+ * launch by packing their weights stacked along cout.  The pack holds the rows padded with zeros
+ * to a multiple of 64; padding rows are never stored to `out`.
+ * bias is [cout], or NULL for no bias.  All tensors fp32, 4-byte aligned.
+ * Arithmetic: one launch, an implicit GEMM with K = 9 cin on the bf16 MFMA with
+ * CORR_BUILD_BF16X6's exact three-piece split (six products per fp32 product, no scales: no
+ * narrower than fp32), fp32 accumulation in a fixed order (32-channel chunk outer, tap inner with
+ * ky major and kx minor), then + bias and the ReLU, each fp32 op rounded once: deterministic.
+ * Finite inputs give finite outputs; non-finite inputs are NOT parity-checked (an infinite
+ * activation meets the zero low pieces of the weights and comes out NaN).
+ * Sizes: ca >= 32 and cb >= 0, each a multiple of 32, ca + cb <= 1024; 1 <= cout <= 1024; any
+ * B, H, W >= 1 with B*H*W < 2^31; other channel counts return CORR_EUNSUPPORTED.  CORR_EINVAL:
+ * a NULL in_a, packed or out; in_b NULL with cb > 0; relu not 0 or 1; out_offset < 0 or
+ * out_offset + cout > out_channels; packed not 16-byte aligned; B, H or W < 1; out overlapping
+ * an input.  Every refusal comes before any HIP call.  No workspace, no allocation, no
+ * synchronisation; the launch goes on `stream` and can be captured into a graph.
+ */
+size_t corr_conv_weights_bytes(int cout, int cin);
+int corr_conv_pack_weights(const float *w, int cout, int cin, void *packed, void *stream);
+int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
+                      const void *packed, const float *bias, int cout, int relu, float *out,
+                      int out_channels, int out_offset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
