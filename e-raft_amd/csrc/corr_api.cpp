@@ -642,6 +642,82 @@ int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int 
                       fn);
 }
 
+size_t corr_enc_stats_bytes(int B, int cout, int Ho, int Wo) {
+    if (B < 1 || cout < 1 || Ho < 1 || Wo < 1) return 0;
+    return enc_stats_bytes(B, cout, Ho, Wo);
+}
+
+int corr_enc_conv_forward(const float *in, int cin, int B, int H, int W, int stride, const float *in_scale,
+                          const float *in_shift, int norm_per_batch, const void *packed, const float *bias,
+                          int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
+    static const char *fn = "corr_enc_conv_forward";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    if (stride != 1 && stride != 2)
+        return fail(CORR_EUNSUPPORTED, "%s: built for stride 1 and 2 (got %d)", fn, stride);
+    if ((rc = check_conv_channels(fn, cout, cin, 0))) return rc;
+    if ((rc = check_ptr(fn, in, "in")) || (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, out, "out")))
+        return rc;
+    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    if (!in_scale != !in_shift)
+        return fail(CORR_EINVAL, "%s: in_scale and in_shift must both be given or both be NULL", fn);
+    if (in_scale && ((rc = check_ptr(fn, in_scale, "in_scale")) || (rc = check_ptr(fn, in_shift, "in_shift"))))
+        return rc;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    if (stats) {
+        if ((rc = check_ptr(fn, stats, "stats"))) return rc;
+        const size_t need = enc_stats_bytes(B, cout, Ho, Wo);
+        if (stats_bytes < need)
+            return fail(CORR_EINVAL, "%s: stats of %zu bytes needed, got %zu", fn, need, stats_bytes);
+    }
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    const long double ib = (long double)B * H * W * sizeof(float) * cin;
+    const long double ob = (long double)B * Ho * Wo * sizeof(float) * cout;
+    if (ranges_overlap(out, ob, in, ib)) return fail(CORR_EINVAL, "%s: out must not overlap in", fn);
+    return hip_status(launch_enc_conv(in, cin, B, H, W, stride, in_scale, in_shift, norm_per_batch != 0, packed, bias,
+                                      cout, out, static_cast<float *>(stats), (hipStream_t)stream),
+                      fn);
+}
+
+// B, C, H, W of the finalize and the join: every plane and the [B][C] tables are int-indexed
+static int check_enc_planes(const char *fn, int B, int C, int H, int W) {
+    if (B < 1 || C < 1 || H < 1 || W < 1)
+        return fail(CORR_EINVAL, "%s: B, C, H, W must be >= 1 (got %d, %d, %d, %d)", fn, B, C, H, W);
+    if ((long long)B * C > (1LL << 31) - 1 || (long long)H * W > (1LL << 30))
+        return fail(CORR_EINVAL, "%s: B*C or H*W too large", fn);
+    return CORR_OK;
+}
+
+int corr_enc_norm_finalize(const void *stats, int B, int C, int Ho, int Wo, float eps, float *scale, float *shift,
+                           void *stream) {
+    static const char *fn = "corr_enc_norm_finalize";
+    g_err[0] = 0;
+    int rc = check_enc_planes(fn, B, C, Ho, Wo);
+    if (rc) return rc;
+    if (!(eps > 0.f)) return fail(CORR_EINVAL, "%s: eps must be positive", fn);
+    if ((rc = check_ptr(fn, stats, "stats")) || (rc = check_ptr(fn, scale, "scale")) ||
+        (rc = check_ptr(fn, shift, "shift")))
+        return rc;
+    return hip_status(launch_enc_finalize(static_cast<const float *>(stats), B, C, Ho, Wo, eps, scale, shift,
+                                          (hipStream_t)stream),
+                      fn);
+}
+
+int corr_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch, const float *skip,
+                  int B, int C, int H, int W, float *out, void *stream) {
+    static const char *fn = "corr_enc_join";
+    g_err[0] = 0;
+    int rc = check_enc_planes(fn, B, C, H, W);
+    if (rc) return rc;
+    if ((rc = check_ptr(fn, y, "y")) || (rc = check_ptr(fn, scale, "scale")) || (rc = check_ptr(fn, shift, "shift")) ||
+        (rc = check_ptr(fn, skip, "skip")) || (rc = check_ptr(fn, out, "out")))
+        return rc;
+    return hip_status(launch_enc_join(y, scale, shift, norm_per_batch != 0, skip, B, C, H, W, out, (hipStream_t)stream),
+                      fn);
+}
+
 int corr_convex_upsample(const float *flow, const float *mask, int N, int h, int w, float *out, void *stream) {
     static const char *fn = "corr_convex_upsample";
     g_err[0] = 0;

@@ -216,6 +216,16 @@ hipError_t launch_conv_pack(const float *w, int cout, int cin, void *packed, hip
 hipError_t launch_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
                                const void *packed, const float *bias, int cout, int relu, float *out,
                                int out_channels, int out_offset, hipStream_t s);
+// The encoders' residual stages (corr_conv.hip): the same convolution at stride 1 or 2 with norm
+// on load and per-tile statistics, the statistics' merge, and the block's join.
+size_t enc_stats_bytes(int B, int cout, int Ho, int Wo);
+hipError_t launch_enc_conv(const float *in, int cin, int B, int H, int W, int stride, const float *scale,
+                           const float *shift, int norm_per_batch, const void *packed, const float *bias, int cout,
+                           float *out, float *stats, hipStream_t s);
+hipError_t launch_enc_finalize(const float *stats, int B, int C, int Ho, int Wo, float eps, float *scale,
+                               float *shift, hipStream_t s);
+hipError_t launch_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch,
+                           const float *skip, int B, int C, int H, int W, float *out, hipStream_t s);
 size_t build_bwd_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bwd(const float *grad_c, const float *f1, int NQ, const float *f2, int B,
                             int D, int H, int W, float *df1, float *df2, float *ws, hipStream_t s);

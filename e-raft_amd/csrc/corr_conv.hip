@@ -1,6 +1,6 @@
 // corr_conv.hip — a 3x3 convolution (padding 1, stride 1) with bias and an optional ReLU on
 // gfx950, inference only: the update block's convc2, convf2, conv and the two heads' first
-// convolutions (model/update.py:63-107).
+// convolutions (model/update.py:63-107); and its forms for the encoders' residual stages.
 //
 //   out[b][out_offset + o][y][x] = act(bias[o] + sum_c sum_ky sum_kx w[o][c][ky][kx] in[b][c][y+ky-1][x+kx-1])
 //
@@ -32,6 +32,13 @@
 // rows are computed and never stored), and streamed from L2 kConvAhead K steps ahead in a ring.
 // No atomics, no scratch, nothing allocated.
 //
+// The same kernel is a template <STRIDE, NORM_IN, STATS> for the encoders' residual stages
+// (model/extractor.py:7-52; launch_enc_conv): stride 2 (a 9 x 33 window, staged by
+// another thread-to-word map), a per-channel affine + ReLU applied while staging (the norm of the
+// producing convolution, "norm on load"), and per-tile (sum, M2) statistics of the output for that
+// norm, merged by enc_finalize_kernel; enc_join_kernel is the block's normalise + add + ReLU.
+// <1, false, false> is the kernel described above, unchanged in its arithmetic.
+//
 // Non-finite inputs are not parity-checked (an infinite activation meets the zero mid / lo
 // pieces of the weights); finite inputs give finite outputs.
 #include <type_traits>
@@ -47,9 +54,22 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kConvTW = 16, kConvTH = 4;       // pixel tile (columns x rows)
-constexpr int kConvPW = kConvTW + 2;           // staged positions per row
-constexpr int kConvPH = kConvTH + 2;           // staged rows
-constexpr int kConvNPOS = kConvPW * kConvPH;   // 108
+// The staged window of a 4 x 16 output tile at stride S: S (t - 1) + 3 positions a side.
+template <int S>
+struct ConvGeo {
+    static constexpr int PW = kConvTW * S + 3 - S;             // staged positions per row: 18 / 33
+    static constexpr int PH = kConvTH * S + 3 - S;             // staged rows: 6 / 9
+    static constexpr int NPOS = PW * PH;                       // 108 / 297
+    static constexpr int Stage = NPOS * 16;                    // staged words per piece and chunk: 1728 / 4752
+    // Staging passes per thread.  Stride 1: word idx = tid + 256 i of the chunk's Stage words, 7
+    // passes, the last guarded.  Stride 2: a wave owns 4 channel pairs and a lane the positions
+    // lane + 64 i, i < NPP = 5 (the last guarded), so only NPP positions' bookkeeping is live and
+    // the channel pair is wave-uniform: 19 passes of the stride-1 scheme would hold 4 registers of
+    // it each.
+    static constexpr int NPP = S == 1 ? 0 : (NPOS + 63) / 64;
+    static constexpr int NLD = S == 1 ? (Stage + 256 - 1) / 256 : 4 * NPP;
+    static constexpr int Ahead = S == 1 ? 2 : 1;               // chunks the activation registers run ahead
+};
 constexpr int kConvT = 1;                      // 16-row blocks per wave (2 measured slower)
 constexpr int kConvOB = 32 * kConvT;           // output rows per workgroup
 constexpr int kConvPad = 64;                   // the pack pads the rows to a multiple of this
@@ -59,11 +79,11 @@ constexpr int kConvTaps = 9;
 constexpr int kConvWaves = 2;                  // waves per SIMD the kernel is compiled for (<= 256 registers)
 constexpr int kConvRing = 6;                   // weight ring slots; divides the 18 K steps of a chunk pair
 constexpr int kConvAhead = 5;                  // K steps the weight fragments run ahead (< kConvRing)
-constexpr int kConvStage = kConvNPOS * 16;     // staged words per piece and chunk: 1728
-constexpr int kConvNLD = (kConvStage + kConvNT - 1) / kConvNT;  // staging passes per thread: 7, the last guarded
+constexpr int kConvMaxCin = 1024;              // conv_supported's bound (the norm-on-load table in LDS)
 static_assert((2 * kConvTaps) % kConvRing == 0 && kConvAhead < kConvRing, "ring slots are compile-time");
-static_assert(kConvStage - (kConvNLD - 1) * kConvNT > 0 && (kConvStage - (kConvNLD - 1) * kConvNT) % 64 == 0,
-              "the guard of the last staging pass is wave-uniform");
+static_assert(kConvNT == 256 && ConvGeo<1>::Stage - (ConvGeo<1>::NLD - 1) * kConvNT > 0 &&
+                  (ConvGeo<1>::Stage - (ConvGeo<1>::NLD - 1) * kConvNT) % 64 == 0,
+              "the guard of the last staging pass is wave-uniform at stride 1");
 
 __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
@@ -96,37 +116,73 @@ __global__ __launch_bounds__(64) void conv_pack_kernel(const float *__restrict__
 }
 
 struct ConvArgs {
-    const float *a;     // channels < ca of the input
-    const float *b;     // the other cb channels (unused when cb == 0)
-    const float *bias;  // [cout], or null for no bias
-    const u32x4 *frag;  // the pack
-    float *out;         // [B][oc][H][W]; channels off .. off + cout - 1 are written
-    int B, ca, cb, H, W, cout, relu, oc, off, tx, ty;
+    const float *a;      // channels < ca of the input
+    const float *b;      // the other cb channels (unused when cb == 0)
+    const float *bias;   // [cout], or null for no bias
+    const u32x4 *frag;   // the pack
+    float *out;          // [B][oc][Ho][Wo]; channels off .. off + cout - 1 are written
+    const float *scale;  // NORM_IN: [B][cin] (nb = 1) or [cin] (nb = 0)
+    const float *shift;
+    float *stats;        // STATS: [B][cout][tiles][2]
+    int B, ca, cb, H, W, cout, relu, oc, off, tx, ty, nb;
 };
 
+// STRIDE 1 or 2 (padding 1, Ho = (H - 1) / STRIDE + 1; tx, ty tile the output).  NORM_IN: a staged
+// value is relu(in * scale[c] + shift[c]) (two fp32 ops, each rounded), and the zero of a position
+// outside the map is applied after it: the padding is zero in the normalised domain.  STATS: no
+// ReLU, and the workgroup leaves (sum, M2 about the tile's own mean) of its valid pixels per
+// output channel (header: corr_enc_conv_forward).
+template <int STRIDE, bool NORM_IN, bool STATS>
 __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
+    using G = ConvGeo<STRIDE>;
+    constexpr int kConvPW = G::PW, kConvNPOS = G::NPOS, kConvStage = G::Stage, kConvNLD = G::NLD;
     __shared__ __attribute__((aligned(16))) unsigned xs[3][kConvNPOS][kConvXS];
+    __shared__ float nrm[NORM_IN ? 2 * kConvMaxCin : 1];  // scale | shift of this batch item's channels
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int H = g.H, W = g.W;
+    const int Ho = STRIDE == 1 ? H : (H - 1) / STRIDE + 1, Wo = STRIDE == 1 ? W : (W - 1) / STRIDE + 1;
     const size_t HW = (size_t)H * W;
     const int tiles = g.tx * g.ty;
     const int b = blockIdx.x / tiles, tl = blockIdx.x - b * tiles;
     const int y0 = (tl / g.tx) * kConvTH, x0 = (tl % g.tx) * kConvTW;
     const int NC = (g.ca + g.cb) / 32, NS = NC * kConvTaps;
 
-    // ---- staging: pass i of this thread is channel pair kp[i] at position ps[i] ----
-    int ps[kConvNLD], kp[kConvNLD];
-    long off[kConvNLD];  // float offset inside a batch item's chunk (0 for a position outside the map)
+    if constexpr (NORM_IN) {
+        const int cin = g.ca + g.cb;
+        const size_t base = g.nb ? (size_t)b * cin : 0;
+        for (int c = tid; c < cin; c += kConvNT) {
+            nrm[c] = g.scale[base + c];
+            nrm[kConvMaxCin + c] = g.shift[base + c];
+        }
+        __syncthreads();
+    }
+
+    // ---- staging: pass i of this thread is channel pair kp[i] at position ps[i] (stride 2: pass
+    // 5 k + i is channel pair 4 w + k at position ps[i]) ----
+    constexpr int kConvNB = STRIDE == 1 ? kConvNLD : G::NPP;  // passes with bookkeeping of their own
+    int ps[kConvNB];
+    [[maybe_unused]] int kp[STRIDE == 1 ? kConvNLD : 1];
+    long off[kConvNB];   // float offset inside a batch item's chunk (0 for a position outside the map)
     unsigned inmap = 0;  // bit i: pass i's position is inside the map (else its values are zero)
+    static_assert(kConvNB <= 32, "one inmap bit per pass");
+    [[maybe_unused]] const int wu = __builtin_amdgcn_readfirstlane(w);
 #pragma unroll
-    for (int i = 0; i < kConvNLD; ++i) {
-        const int idx = tid + kConvNT * i;
-        const bool live = idx < kConvStage;  // false only in the last pass (wave 3)
-        kp[i] = live ? idx / kConvNPOS : 0;
-        ps[i] = live ? idx - kp[i] * kConvNPOS : 0;
-        const int y = y0 + ps[i] / kConvPW - 1, x = x0 + ps[i] % kConvPW - 1;
+    for (int i = 0; i < kConvNB; ++i) {
+        bool live;
+        long plane = 0;
+        if constexpr (STRIDE == 1) {
+            const int idx = tid + kConvNT * i;
+            live = idx < kConvStage;  // false only in the last pass
+            kp[i] = live ? idx / kConvNPOS : 0;
+            ps[i] = live ? idx - kp[i] * kConvNPOS : 0;
+            plane = (long)(2 * kp[i]) * (long)HW;
+        } else {
+            live = lane + 64 * i < kConvNPOS;  // false only in the last pass
+            ps[i] = live ? lane + 64 * i : 0;
+        }
+        const int y = STRIDE * y0 + ps[i] / kConvPW - 1, x = STRIDE * x0 + ps[i] % kConvPW - 1;
         const bool in = live && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-        off[i] = in ? (long)(2 * kp[i]) * (long)HW + (long)y * W + x : 0;
+        off[i] = in ? plane + (long)y * W + x : 0;
         inmap |= (unsigned)in << i;
     }
     // (every load is unconditional, from a valid address, and the zero of a position outside the
@@ -134,10 +190,22 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
     auto load_chunk = [&](int ch, float (&v)[kConvNLD][2]) {
         const int c0 = 32 * ch;
         const float *src = c0 < g.ca ? g.a + ((size_t)b * g.ca + c0) * HW : g.b + ((size_t)b * g.cb + (c0 - g.ca)) * HW;
+        if constexpr (STRIDE == 1) {
 #pragma unroll
-        for (int i = 0; i < kConvNLD; ++i) {
-            v[i][0] = src[off[i]];
-            v[i][1] = src[off[i] + HW];
+            for (int i = 0; i < kConvNLD; ++i) {
+                v[i][0] = src[off[i]];
+                v[i][1] = src[off[i] + HW];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float *sk = src + (size_t)(2 * (4 * wu + k)) * HW;
+#pragma unroll
+                for (int i = 0; i < G::NPP; ++i) {
+                    v[G::NPP * k + i][0] = sk[off[i]];
+                    v[G::NPP * k + i][1] = sk[off[i] + HW];
+                }
+            }
         }
     };
 
@@ -163,11 +231,13 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
     // The weights run kConvAhead K steps ahead of the products in a ring (step s lives in slot
     // s % kConvRing; a pair of chunks is 18 steps, so the slot of (chunk parity, tap) is a
     // constant), the activations two chunks ahead in two register sets: at DSEC a CU holds one or
-    // two workgroups, too few to hide an L2 round trip per step.
+    // two workgroups, too few to hide an L2 round trip per step.  (Stride 2 stages 2.75 times as
+    // many values per chunk and keeps one set, one chunk ahead.)
     u32x4 wa[kConvRing][kConvT][3];
-    float va[kConvNLD][2], vb[kConvNLD][2];
+    float va[kConvNLD][2];
+    [[maybe_unused]] float vb[G::Ahead == 2 ? kConvNLD : 1][2];
     load_chunk(0, va);
-    load_chunk(NC > 1 ? 1 : 0, vb);
+    if constexpr (G::Ahead == 2) load_chunk(NC > 1 ? 1 : 0, vb);
 #pragma unroll
     for (int s = 0; s < kConvAhead; ++s) load_a(wa[s], s);
     auto chunk = [&](int ch, auto par, float (&v)[kConvNLD][2]) {
@@ -175,16 +245,27 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
 #pragma unroll
         for (int i = 0; i < kConvNLD; ++i) {
             unsigned hi, mid, lo;
-            const bool in = (inmap >> i) & 1;
-            split3(in ? v[i][0] : 0.f, in ? v[i][1] : 0.f, hi, mid, lo);
-            if (i + 1 < kConvNLD || tid + kConvNT * i < kConvStage) {
-                xs[0][ps[i]][kp[i]] = hi;
-                xs[1][ps[i]][kp[i]] = mid;
-                xs[2][ps[i]][kp[i]] = lo;
+            const int ib = STRIDE == 1 ? i : i % (G::NPP ? G::NPP : 1);  // this pass's bookkeeping
+            const int kpi = STRIDE == 1 ? kp[STRIDE == 1 ? i : 0] : 4 * wu + i / (G::NPP ? G::NPP : 1);
+            const bool in = (inmap >> ib) & 1;
+            float p = v[i][0], q = v[i][1];
+            if constexpr (NORM_IN) {
+                const int c = 32 * ch + 2 * kpi;
+                p = p * nrm[c] + nrm[kConvMaxCin + c];
+                q = q * nrm[c + 1] + nrm[kConvMaxCin + c + 1];
+                p = p < 0.f ? 0.f : p;
+                q = q < 0.f ? 0.f : q;
+            }
+            split3(in ? p : 0.f, in ? q : 0.f, hi, mid, lo);
+            if (STRIDE == 1 ? i + 1 < kConvNLD || tid + kConvNT * i < kConvStage
+                            : ib + 1 < G::NPP || lane + 64 * ib < kConvNPOS) {
+                xs[0][ps[ib]][kpi] = hi;
+                xs[1][ps[ib]][kpi] = mid;
+                xs[2][ps[ib]][kpi] = lo;
             }
         }
         __syncthreads();
-        load_chunk(ch + 2 < NC ? ch + 2 : NC - 1, v);  // (past the end: a harmless re-read)
+        load_chunk(ch + G::Ahead < NC ? ch + G::Ahead : NC - 1, v);  // (past the end: a harmless re-read)
 #pragma unroll
         for (int tap = 0; tap < kConvTaps; ++tap) {
             load_a(wa[(S0 + tap + kConvAhead) % kConvRing], ch * kConvTaps + tap + kConvAhead);
@@ -194,7 +275,8 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
             for (int c = 0; c < 2; ++c)
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
-                    xb[c][p] = *reinterpret_cast<const u32x4 *>(&xs[p][(j0 + c) * kConvPW + fr + tp][fk]);
+                    xb[c][p] = *reinterpret_cast<const u32x4 *>(
+                        &xs[p][STRIDE * ((j0 + c) * kConvPW + fr) + tp][fk]);
 #pragma unroll
             for (int t = 0; t < kConvT; ++t) {
                 const u32x4 wh = wa[(S0 + tap) % kConvRing][t][0], wm = wa[(S0 + tap) % kConvRing][t][1],
@@ -216,33 +298,153 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
 #pragma unroll 1
     for (; ch + 1 < NC; ch += 2) {
         chunk(ch, std::integral_constant<int, 0>{}, va);
-        chunk(ch + 1, std::integral_constant<int, 1>{}, vb);
+        if constexpr (G::Ahead == 2)
+            chunk(ch + 1, std::integral_constant<int, 1>{}, vb);
+        else
+            chunk(ch + 1, std::integral_constant<int, 1>{}, va);
     }
     if (ch < NC) chunk(ch, std::integral_constant<int, 0>{}, va);
 
     // ---- epilogue: C[row = 4 (lane >> 4) + r][col = lane & 15] ----
+    const size_t HWo = (size_t)Ho * Wo;
     const int x = x0 + fr;
-    if (x >= W) return;
+    if constexpr (!STATS) {
+        if (x >= Wo) return;
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int y = y0 + j0 + c;
-        if (y >= H) continue;
-        const size_t n = (size_t)y * W + x;
+        for (int c = 0; c < 2; ++c) {
+            const int y = y0 + j0 + c;
+            if (y >= Ho) continue;
+            const size_t n = (size_t)y * Wo + x;
 #pragma unroll
-        for (int t = 0; t < kConvT; ++t)
+            for (int t = 0; t < kConvT; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = (int)blockIdx.y * kConvOB + 16 * kConvT * (w & 1) + 16 * t + 4 * (lane >> 4) + r;
-                if (row >= g.cout) continue;  // a padding row of the pack
-                float v = split_sum(acc[t][c][r], acs[t][c][r]);
-                if (g.bias) v = v + g.bias[row];
-                if (g.relu) v = v < 0.f ? 0.f : v;
-                g.out[((size_t)b * g.oc + g.off + row) * HW + n] = v;
+                for (int r = 0; r < 4; ++r) {
+                    const int row = (int)blockIdx.y * kConvOB + 16 * kConvT * (w & 1) + 16 * t + 4 * (lane >> 4) + r;
+                    if (row >= g.cout) continue;  // a padding row of the pack
+                    float v = split_sum(acc[t][c][r], acs[t][c][r]);
+                    if (g.bias) v = v + g.bias[row];
+                    if (g.relu) v = v < 0.f ? 0.f : v;
+                    g.out[((size_t)b * g.oc + g.off + row) * HWo + n] = v;
+                }
+        }
+    } else {
+        // Every lane stays (the reductions and the barrier need all of them); a pixel past Ho / Wo
+        // is neither stored nor counted.  Per output row: the 16 columns by 2 tile rows of a wave
+        // are summed by a butterfly over the 16 lanes of a row group (every lane ends with the
+        // same bits: each level adds the same two values in either order), the squared deviations
+        // from that half's mean likewise; the two halves of the tile (waves w and w + 2) meet in
+        // LDS and thread `row` merges them, upper half first (Chan et al.).
+        static_assert(kConvT == 1, "the statistics epilogue is written for one row block per wave");
+        float *red = reinterpret_cast<float *>(&xs[0][0][0]);  // [half][32 rows][sum, M2]; the tile is consumed
+        const int nx = min(kConvTW, Wo - x0);
+        const bool ok[2] = {x < Wo && y0 + j0 < Ho, x < Wo && y0 + j0 + 1 < Ho};
+        const int nyw = max(0, min(2, Ho - (y0 + j0)));
+        const float nw = (float)(nx * nyw);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int lrow = 16 * (w & 1) + 4 * (lane >> 4) + r, row = (int)blockIdx.y * kConvOB + lrow;
+            const bool live = row < g.cout;
+            const float bs = g.bias && live ? g.bias[row] : 0.f;
+            float v[2];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                v[c] = split_sum(acc[0][c][r], acs[0][c][r]) + bs;
+                if (ok[c] && live)
+                    g.out[((size_t)b * g.oc + g.off + row) * HWo + (size_t)(y0 + j0 + c) * Wo + x] = v[c];
             }
+            float s = (ok[0] ? v[0] : 0.f) + (ok[1] ? v[1] : 0.f);
+#pragma unroll
+            for (int m = 1; m < 16; m <<= 1) s = s + __shfl_xor(s, m);
+            const float mean = nyw > 0 ? s / nw : 0.f;
+            const float d0 = ok[0] ? v[0] - mean : 0.f, d1 = ok[1] ? v[1] - mean : 0.f;
+            float q = d0 * d0 + d1 * d1;
+#pragma unroll
+            for (int m = 1; m < 16; m <<= 1) q = q + __shfl_xor(q, m);
+            if (fr == 0) {
+                red[((w >> 1) * kConvOB + lrow) * 2] = s;
+                red[((w >> 1) * kConvOB + lrow) * 2 + 1] = q;
+            }
+        }
+        __syncthreads();
+        const int row = (int)blockIdx.y * kConvOB + tid;
+        if (tid < kConvOB && row < g.cout) {
+            const float na = (float)(nx * min(2, Ho - y0)), nb = (float)(nx * max(0, min(2, Ho - y0 - 2)));
+            const float sa = red[tid * 2], qa = red[tid * 2 + 1];
+            const float sb = red[(kConvOB + tid) * 2], qb = red[(kConvOB + tid) * 2 + 1];
+            float sum = sa, m2 = qa;
+            if (nb > 0.f) {
+                const float d = sb / nb - sa / na;
+                sum = sa + sb;
+                m2 = (qa + qb) + (d * d) * (na * nb / (na + nb));
+            }
+            float *st = g.stats + (((size_t)b * g.cout + row) * tiles + tl) * 2;
+            st[0] = sum;
+            st[1] = m2;
+        }
+    }
+}
+
+// One wave per (b, c): lane l merges tiles l per, .. in ascending order, then the lanes are merged
+// pairwise in ascending order (Chan et al., fp64).  The pixel count of a tile is its geometry's.
+struct Moments {
+    double n, mean, m2;
+};
+__device__ __forceinline__ Moments merge(Moments a, Moments b) {
+    if (b.n == 0.0) return a;
+    if (a.n == 0.0) return b;
+    const double n = a.n + b.n, d = b.mean - a.mean;
+    return Moments{n, a.mean + d * (b.n / n), a.m2 + b.m2 + d * d * (a.n * b.n / n)};
+}
+
+__global__ __launch_bounds__(256) void enc_finalize_kernel(const float *__restrict__ stats, int BC, int Ho, int Wo,
+                                                           int tx, int ty, float eps, float *__restrict__ scale,
+                                                           float *__restrict__ shift) {
+    const int lane = threadIdx.x & 63, bc = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (bc >= BC) return;  // wave-uniform
+    const int tiles = tx * ty, per = (tiles + 63) / 64;
+    const float *st = stats + (size_t)bc * tiles * 2;
+    Moments m{0.0, 0.0, 0.0};
+    for (int t = lane * per; t < min(tiles, (lane + 1) * per); ++t) {
+        const int tyi = t / tx, txi = t - tyi * tx;
+        const double n = (double)(min(kConvTH, Ho - tyi * kConvTH) * min(kConvTW, Wo - txi * kConvTW));
+        m = merge(m, Moments{n, (double)st[2 * t] / n, (double)st[2 * t + 1]});
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const Moments u{__shfl_down(m.n, o), __shfl_down(m.mean, o), __shfl_down(m.m2, o)};
+        if ((lane & (2 * o - 1)) == 0) m = merge(m, u);
+    }
+    if (lane == 0) {
+        const float sc = (float)(1.0 / sqrt(m.m2 / m.n + (double)eps));
+        scale[bc] = sc;
+        shift[bc] = (float)(-m.mean * (double)sc);
+    }
+}
+
+// out = relu(skip + relu(y * scale + shift)); one plane (b, c) per blockIdx.x.  Each element is
+// read and written by the same thread, so out may be y.
+__global__ __launch_bounds__(256) void enc_join_kernel(const float *y, const float *__restrict__ scale,
+                                                       const float *__restrict__ shift, int nb, const float *skip,
+                                                       int C, size_t HW, float *out) {
+    const int bc = blockIdx.x, k = nb ? bc : bc % C;
+    const float sc = scale[k], sh = shift[k];
+    const size_t base = (size_t)bc * HW;
+    for (size_t i = (size_t)blockIdx.y * 256 + threadIdx.x; i < HW; i += (size_t)gridDim.y * 256) {
+        float v = y[base + i] * sc + sh;
+        v = v < 0.f ? 0.f : v;
+        v = skip[base + i] + v;
+        out[base + i] = v < 0.f ? 0.f : v;
     }
 }
 
 constexpr int conv_rows(int cout) { return (cout + kConvPad - 1) / kConvPad * kConvPad; }
+
+template <int STRIDE, bool NORM_IN, bool STATS>
+hipError_t launch_conv(const ConvArgs &g, hipStream_t s) {
+    const dim3 grid((unsigned)g.B * g.tx * g.ty, conv_rows(g.cout) / kConvOB);
+    hipLaunchKernelGGL((conv_kernel<STRIDE, NORM_IN, STATS>), grid, dim3(kConvNT), 0, s, g);
+    return hipGetLastError();
+}
 
 }  // namespace
 
@@ -272,9 +474,55 @@ hipError_t launch_conv_forward(const float *in_a, int ca, const float *in_b, int
     g.B = B, g.ca = ca, g.cb = cb, g.H = H, g.W = W, g.cout = cout, g.relu = relu;
     g.oc = out_channels, g.off = out_offset;
     g.tx = (W + kConvTW - 1) / kConvTW, g.ty = (H + kConvTH - 1) / kConvTH;
-    const dim3 grid((unsigned)B * g.tx * g.ty, conv_rows(cout) / kConvOB);
-    hipLaunchKernelGGL(conv_kernel, grid, dim3(kConvNT), 0, s, g);
+    return launch_conv<1, false, false>(g, s);
+}
+
+static int enc_out(int n, int stride) { return (n - 1) / stride + 1; }
+
+size_t enc_stats_bytes(int B, int cout, int Ho, int Wo) {
+    return (size_t)B * cout * ((Ho + kConvTH - 1) / kConvTH) * ((Wo + kConvTW - 1) / kConvTW) * 2 * sizeof(float);
+}
+
+hipError_t launch_enc_conv(const float *in, int cin, int B, int H, int W, int stride, const float *scale,
+                           const float *shift, int norm_per_batch, const void *packed, const float *bias, int cout,
+                           float *out, float *stats, hipStream_t s) {
+    if (!conv_supported(cout, cin, 0) || (stride != 1 && stride != 2)) return hipErrorInvalidValue;
+    const int Ho = enc_out(H, stride), Wo = enc_out(W, stride);
+    ConvArgs g{};
+    g.a = g.b = in, g.bias = bias;
+    g.frag = static_cast<const u32x4 *>(packed);
+    g.out = out, g.scale = scale, g.shift = shift, g.stats = stats;
+    g.B = B, g.ca = cin, g.cb = 0, g.H = H, g.W = W, g.cout = cout, g.relu = 0, g.oc = cout, g.off = 0;
+    g.tx = (Wo + kConvTW - 1) / kConvTW, g.ty = (Ho + kConvTH - 1) / kConvTH, g.nb = norm_per_batch;
+    const int sel = (stride == 2 ? 4 : 0) | (scale ? 2 : 0) | (stats ? 1 : 0);
+    switch (sel) {
+        case 0: return launch_conv<1, false, false>(g, s);
+        case 1: return launch_conv<1, false, true>(g, s);
+        case 2: return launch_conv<1, true, false>(g, s);
+        case 3: return launch_conv<1, true, true>(g, s);
+        case 4: return launch_conv<2, false, false>(g, s);
+        case 5: return launch_conv<2, false, true>(g, s);
+        case 6: return launch_conv<2, true, false>(g, s);
+        default: return launch_conv<2, true, true>(g, s);
+    }
+}
+
+hipError_t launch_enc_finalize(const float *stats, int B, int C, int Ho, int Wo, float eps, float *scale,
+                               float *shift, hipStream_t s) {
+    const int BC = B * C;
+    hipLaunchKernelGGL(enc_finalize_kernel, dim3((BC + 3) / 4), dim3(256), 0, s, stats, BC, Ho, Wo,
+                       (Wo + kConvTW - 1) / kConvTW, (Ho + kConvTH - 1) / kConvTH, eps, scale, shift);
+    return hipGetLastError();
+}
+
+hipError_t launch_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch,
+                           const float *skip, int B, int C, int H, int W, float *out, hipStream_t s) {
+    const size_t HW = (size_t)H * W;
+    const unsigned gy = (unsigned)((HW + 1023) / 1024 < 4096 ? (HW + 1023) / 1024 : 4096);
+    hipLaunchKernelGGL(enc_join_kernel, dim3((unsigned)(B * C), gy), dim3(256), 0, s, y, scale, shift, norm_per_batch,
+                       skip, C, HW, out);
     return hipGetLastError();
 }
 
 }  // namespace corr
+

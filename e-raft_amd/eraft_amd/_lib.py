@@ -34,7 +34,8 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_pyramid_import", "corr_ondemand_workspace", "corr_ondemand_prepare", "corr_ondemand_lookup",
            "corr_ondemand_bwd_workspace", "corr_ondemand_backward", "corr_gru_weights_bytes",
            "corr_gru_pack_weights", "corr_gru_workspace", "corr_gru_half_step", "corr_conv_weights_bytes",
-           "corr_conv_pack_weights", "corr_conv_forward")
+           "corr_conv_pack_weights", "corr_conv_forward", "corr_enc_stats_bytes", "corr_enc_conv_forward",
+           "corr_enc_norm_finalize", "corr_enc_join")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -152,7 +153,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_conv_weights_bytes.argtypes, lib.corr_conv_weights_bytes.restype = [i, i], sz
     lib.corr_conv_pack_weights.argtypes = [vp, i, i, vp, vp]
     lib.corr_conv_forward.argtypes = [vp, i, vp, i, i, i, i, vp, vp, i, i, vp, i, i, vp]
-    for f in ("corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
+    lib.corr_enc_stats_bytes.argtypes, lib.corr_enc_stats_bytes.restype = [i, i, i, i], sz
+    lib.corr_enc_conv_forward.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, sz, vp]
+    lib.corr_enc_norm_finalize.argtypes = [vp, i, i, i, i, ctypes.c_float, vp, vp, vp]
+    lib.corr_enc_join.argtypes = [vp, vp, vp, i, vp, i, i, i, i, vp, vp]
+    for f in ("corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
@@ -741,4 +746,87 @@ def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0):
     with torch.cuda.device(in_a.device):
         _check(lib.corr_conv_forward(ap, ca, bp, cb, B, H, W, pk, biasp, cout, int(bool(relu)), op, out.shape[1],
                                      out_offset, _stream(in_a)))
+    return out
+
+
+def _enc_norm(scale, shift, B, C, device, name):
+    """(scale ptr, shift ptr, norm_per_batch) of a [B, C] (per batch item) or [C] (per channel)
+    pair of fp32 tensors."""
+    sp, hp = _dev(scale, f"{name}_scale"), _dev(shift, f"{name}_shift")
+    if scale.shape != shift.shape or tuple(scale.shape) not in ((B, C), (C,)) or scale.device != device \
+            or shift.device != device:
+        raise ValueError(f"{name}_scale / {name}_shift must both be [{B}, {C}] or [{C}] on {device} "
+                         f"(got {tuple(scale.shape)}, {tuple(shift.shape)})")
+    return sp, hp, int(scale.dim() == 2)
+
+
+def enc_conv_forward(x, packed, bias, cout, stride=1, in_scale=None, in_shift=None, stats=False):
+    """corr_enc_conv_forward: the 3x3 convolution (padding 1, stride 1 or 2, + bias, no ReLU) of
+    x [B, cin, H, W], or of relu(x * in_scale + in_shift) when the pair ([B, cin] or [cin]) is
+    given, with the pack of conv_pack_weights.  Returns out [B, cout, Ho, Wo], or (out, stats) with
+    the per-tile statistics buffer for enc_norm_finalize when `stats`."""
+    xp = _dev(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, cin, H, W] (got {tuple(x.shape)})")
+    B, cin, H, W = x.shape
+    lib = load()
+    need = lib.corr_conv_weights_bytes(cout, cin)
+    if need == 0 or stride not in (1, 2):
+        raise CorrError(CORR_EUNSUPPORTED,
+                        f"corr_enc_conv_forward: unsupported cout = {cout}, cin = {cin}, stride = {stride}")
+    pk = _dev(packed, "packed")
+    if packed.numel() * 4 < need or packed.device != x.device:
+        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
+                         f"{need} on {x.device}")
+    biasp = None
+    if bias is not None:
+        biasp = _dev(bias, "bias")
+        if bias.numel() != cout or bias.device != x.device:
+            raise ValueError(f"bias must hold cout = {cout} values on {x.device} (got {tuple(bias.shape)})")
+    if (in_scale is None) != (in_shift is None):
+        raise ValueError("in_scale and in_shift must both be given or both be None")
+    sp, hp, nb = (None, None, 0) if in_scale is None else _enc_norm(in_scale, in_shift, B, cin, x.device, "in")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    out = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    st, nst = None, 0
+    if stats:
+        nst = lib.corr_enc_stats_bytes(B, cout, Ho, Wo)
+        st = torch.empty(nst // 4, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib.corr_enc_conv_forward(xp, cin, B, H, W, stride, sp, hp, nb, pk, biasp, cout, out.data_ptr(),
+                                         None if st is None else st.data_ptr(), nst, _stream(x)))
+    return (out, st) if stats else out
+
+
+def enc_norm_finalize(stats, B, C, Ho, Wo, eps=1e-5):
+    """corr_enc_norm_finalize: the statistics of enc_conv_forward -> (scale, shift), [B, C] each:
+    scale = 1 / sqrt(var + eps) (biased variance over Ho x Wo), shift = -mean * scale."""
+    sp = _dev(stats, "stats")
+    lib = load()
+    if stats.numel() * 4 < lib.corr_enc_stats_bytes(B, C, Ho, Wo) or lib.corr_enc_stats_bytes(B, C, Ho, Wo) == 0:
+        raise ValueError(f"stats holds {stats.numel() * 4} bytes, [{B}, {C}, {Ho}, {Wo}] needs "
+                         f"{lib.corr_enc_stats_bytes(B, C, Ho, Wo)}")
+    scale = torch.empty((B, C), dtype=torch.float32, device=stats.device)
+    shift = torch.empty((B, C), dtype=torch.float32, device=stats.device)
+    with torch.cuda.device(stats.device):
+        _check(lib.corr_enc_norm_finalize(sp, B, C, Ho, Wo, eps, scale.data_ptr(), shift.data_ptr(), _stream(stats)))
+    return scale, shift
+
+
+def enc_join(y, scale, shift, skip, out=None):
+    """corr_enc_join: relu(skip + relu(y * scale + shift)) for y, skip [B, C, H, W] and scale,
+    shift [B, C] or [C]; into `out` (which may be y; allocated when None)."""
+    yp, kp = _dev(y, "y"), _dev(skip, "skip")
+    if y.dim() != 4 or skip.shape != y.shape or skip.device != y.device:
+        raise ValueError(f"y and skip must be equal [B, C, H, W] tensors on one device "
+                         f"(got {tuple(y.shape)}, {tuple(skip.shape)})")
+    B, C, H, W = y.shape
+    sp, hp, nb = _enc_norm(scale, shift, B, C, y.device, "norm")
+    if out is None:
+        out = torch.empty_like(y)
+    op = _dev(out, "out")
+    if out.shape != y.shape or out.device != y.device:
+        raise ValueError(f"out {tuple(out.shape)} does not match y {tuple(y.shape)}")
+    with torch.cuda.device(y.device):
+        _check(load().corr_enc_join(yp, sp, hp, nb, kp, B, C, H, W, op, _stream(y)))
     return out

@@ -83,14 +83,53 @@ class BasicEncoder(nn.Module):
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
 
+    # ERAFT_AMD_FUSE_ENCODER=1: at inference on the MI355X the residual stages' 3x3 convolutions
+    # are corr_enc_conv_forward launches with the norms applied on load (encoder.py) instead of
+    # MIOpen convolutions and torch norm / ReLU / add kernels.  Default off (DESIGN §16 has the
+    # measurements); training always runs the torch code.
+    fused = os.environ.get("ERAFT_AMD_FUSE_ENCODER", "0") == "1"
+
+    def _fusable(self, x):
+        """encoder.encoder_forward is built for an fp32 GPU tensor, instance norm or eval-mode
+        batch norm, the reference's channel counts, and has no backward."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            return False
+        if not (self.norm_fn == "instance" or (self.norm_fn == "batch" and not self.training)):
+            return False
+        if self.training and self.dropout is not None:
+            return False
+        cin = 64
+        for layer, cout, stride in ((self.layer1, 64, 1), (self.layer2, 96, 2), (self.layer3, 128, 2)):
+            for k, blk in enumerate(layer):
+                s = stride if k == 0 else 1
+                if (tuple(blk.conv1.weight.shape) != (cout, cin, 3, 3) or tuple(blk.conv2.weight.shape) != (cout, cout, 3, 3)
+                        or blk.conv1.stride != (s, s) or blk.conv2.stride != (1, 1) or blk.conv1.bias is None
+                        or blk.conv2.bias is None or (blk.downsample is None) != (s == 1)):
+                    return False
+                for n in (blk.norm1, blk.norm2):
+                    if self.norm_fn == "instance":
+                        if not isinstance(n, nn.InstanceNorm2d) or n.affine or n.track_running_stats:
+                            return False
+                    elif not isinstance(n, nn.BatchNorm2d) or n.running_mean is None or n.running_var is None:
+                        return False
+                cin = cout
+        ts = list(self.parameters()) + list(self.buffers())
+        if any(t.device != x.device or (t.is_floating_point() and t.dtype != torch.float32) for t in ts):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, *self.parameters())))
+
     def forward(self, x):
         pair = isinstance(x, (list, tuple))
         if pair:
             n = x[0].shape[0]
             x = torch.cat(x, dim=0)
-        x = self.relu1(self.norm1(self.conv1(x)))
-        x = self.layer3(self.layer2(self.layer1(x)))
-        x = self.conv2(x)
+        if self.fused and self._fusable(x):
+            from .encoder import encoder_forward
+            x = encoder_forward(self, x)
+        else:
+            x = self.relu1(self.norm1(self.conv1(x)))
+            x = self.layer3(self.layer2(self.layer1(x)))
+            x = self.conv2(x)
         if self.training and self.dropout is not None:
             x = self.dropout(x)
         return torch.split(x, [n, n], dim=0) if pair else x

@@ -543,6 +543,56 @@ int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int 
                       const void *packed, const float *bias, int cout, int relu, float *out,
                       int out_channels, int out_offset, void *stream);
 
+/*
+ * The encoders' residual stages (model/extractor.py: ResidualBlock with norm_fn "instance" or,
+ * in eval mode, "batch"), inference only.  A block is
+ *   y1 = conv1(x) [stride 1 or 2];  y2 = conv2(relu(norm1(y1)));  out = relu(skip + relu(norm2(y2)))
+ * and runs as corr_enc_conv_forward (statistics) -> corr_enc_norm_finalize -> corr_enc_conv_forward
+ * (norm on load, statistics) -> corr_enc_norm_finalize -> corr_enc_join.  An eval-mode batch norm
+ * passes its own scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale
+ * with norm_per_batch = 0 and needs neither statistics nor finalize.
+ *
+ * corr_enc_conv_forward: the 3x3 convolution of corr_conv_forward (same pack, from
+ * corr_conv_pack_weights; same arithmetic, K order and six-product order) at stride 1 or 2 with
+ * zero padding 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1 (odd sizes allowed), bias
+ * and no ReLU:
+ *   out[b][o][y][x] = bias[o] + sum_c sum_ky sum_kx w[o][c][ky][kx] * n(in)[b][c][stride y + ky - 1][stride x + kx - 1]
+ * in is [B][cin][H][W], out [B][cout][Ho][Wo].  With in_scale and in_shift given,
+ *   n(v)[b][c] = max(v * in_scale[k] + in_shift[k], 0),  k = b cin + c (norm_per_batch = 1: [B][cin])
+ *                                                         or c (norm_per_batch = 0: [cin]),
+ * two fp32 operations rounded separately, then the max; with both NULL, n(v) = v.  Positions
+ * outside the map are zero AFTER n: the padding is zero in the normalised domain.
+ * stats (may be NULL) receives one pair of floats per (batch item, output channel, 4 x 16 pixel
+ * tile of the output), layout [B][cout][ceil(Ho/4) * ceil(Wo/16)][2], tiles row-major: the sum of
+ * out over the tile's pixels inside the map, and the sum of their squared deviations from that
+ * tile's own mean.  Within a tile the values are combined in a fixed order (no atomics):
+ * deterministic.  stats_bytes must be >= corr_enc_stats_bytes(B, cout, Ho, Wo), which is exactly
+ * the bytes written (0 for sizes < 1); nothing past it is touched.
+ *
+ * corr_enc_norm_finalize: merges the tile pairs of each (b, c) in ascending tile order (Chan et
+ * al.'s pairwise update, fp64; a tile's pixel count follows from Ho, Wo) into the biased variance
+ * and writes scale[b][c] = 1 / sqrt(var + eps), shift[b][c] = -mean * scale as fp32 ([B][C] each):
+ * InstanceNorm2d without affine parameters.  Ho * Wo = 1 gives scale = 1 / sqrt(eps).
+ *
+ * corr_enc_join: out = max(skip + max(y * scale[k] + shift[k], 0), 0) elementwise on [B][C][H][W]
+ * tensors, k as above; each fp32 op rounded once.  out may be y (or skip) itself.
+ *
+ * Sizes: cin a multiple of 32 in 32 .. 1024 and 1 <= cout <= 1024, stride 1 or 2, otherwise
+ * CORR_EUNSUPPORTED.  CORR_EINVAL: a NULL in, packed or out (finalize: stats, scale, shift; join:
+ * y, scale, shift, skip, out); exactly one of in_scale / in_shift NULL; stats with stats_bytes too
+ * small; packed not 16-byte aligned; B, C, H or W < 1 or B*H*W >= 2^31 (B*C >= 2^31); eps not
+ * positive; out overlapping in.  Every refusal comes before any HIP call.  No allocation, no
+ * synchronisation; everything goes on `stream` and can be captured into a graph.
+ */
+size_t corr_enc_stats_bytes(int B, int cout, int Ho, int Wo);
+int corr_enc_conv_forward(const float *in, int cin, int B, int H, int W, int stride, const float *in_scale,
+                          const float *in_shift, int norm_per_batch, const void *packed, const float *bias,
+                          int cout, float *out, void *stats, size_t stats_bytes, void *stream);
+int corr_enc_norm_finalize(const void *stats, int B, int C, int Ho, int Wo, float eps, float *scale,
+                           float *shift, void *stream);
+int corr_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch,
+                  const float *skip, int B, int C, int H, int W, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

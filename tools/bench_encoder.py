@@ -1,0 +1,215 @@
+"""The encoders' residual stages on corr_enc_conv_forward vs the torch / MIOpen ops they replace.
+Every variant is captured as one HIP graph and replayed; the variants of a measurement are
+alternated in ONE process on the same inputs, so box-to-box spread drops out.
+    python tools/bench_encoder.py [--sizes dsec,b8,hires1920] [--trials 5] [--json profiles/encoder_bench.json]
+Per size (the encoder's input; fnet sees both voxel grids as one batch, cnet one) and per encoder
+(fnet: instance norm, cnet: eval-mode batch norm):
+  (a) each kind of convolution against the torch ops it replaces.  "first": a block's conv1 (at
+      its stride), torch conv + norm + ReLU against the kernel with statistics + finalize (instance)
+      or the kernel alone (batch; the norm and the ReLU are its consumer's).  "second": a block's
+      conv2, torch conv + norm + ReLU + add + ReLU against the kernel with norm on load (and
+      statistics + finalize) + join;
+  (b) one whole encoder call with the switch off, with every convolution on the kernel ("all"), and
+      with the committed table encoder.USE_KERNEL ("fused").
+Median / min / max ms per call over the trial windows; for (a) each path's norm-relative error
+against the same formula in fp64 on the GPU, for (b) the kernel path's norm-relative difference
+from the torch path (the parity against the reference is tests/test_encoder.py's).  Prints one JSON
+document; --json also writes it to a file."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "e-raft_amd"))
+from eraft_amd import _lib, encoder  # noqa: E402
+from eraft_amd.model import BasicEncoder  # noqa: E402
+
+# name: (pairs per batch, C_in, H, W) of the model input
+SIZES = {"dsec": (1, 15, 480, 640), "b8": (8, 15, 288, 384), "hires1920": (1, 15, 1280, 1920)}
+# key of encoder.USE_KERNEL: (layer, block, first conv?)
+KINDS = {"layer1.first": ("layer1", 0, True), "layer1.second": ("layer1", 0, False),
+         "layer2.s2": ("layer2", 0, True), "layer2.first": ("layer2", 1, True), "layer2.second": ("layer2", 0, False),
+         "layer3.s2": ("layer3", 0, True), "layer3.first": ("layer3", 1, True), "layer3.second": ("layer3", 0, False)}
+
+
+def norm_rel(a, b):
+    return float((a.double() - b.double()).abs().max() / b.double().abs().max())
+
+
+def norm64(norm, y):
+    """norm(y) in fp64 on the GPU (instance norm without affine, or eval-mode batch norm)."""
+    if isinstance(norm, torch.nn.InstanceNorm2d):
+        return F.instance_norm(y, eps=norm.eps)
+    return F.batch_norm(y, norm.running_mean.double(), norm.running_var.double(), norm.weight.double(),
+                        norm.bias.double(), False, 0.0, norm.eps)
+
+
+def conv64(conv, x):
+    return F.conv2d(x.double(), conv.weight.double(), conv.bias.double(), stride=conv.stride, padding=1)
+
+
+def capture(fn, stream):
+    """fn warmed up twice (MIOpen's solver search, the weight packs), then captured."""
+    torch.cuda.synchronize()  # the inputs were made on the default stream
+    with torch.no_grad(), torch.cuda.stream(stream):
+        for _ in range(2):
+            out = fn()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=stream):
+            keep = fn()
+    torch.cuda.synchronize()
+    return gr, out, keep
+
+
+def alternate(graphs, trials, budget=0.15):
+    """Windows of about `budget` seconds each (sized by the first variant's replay time)."""
+    g0 = next(iter(graphs.values()))
+    g0.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    g0.replay()
+    torch.cuda.synchronize()
+    steps = max(3, min(200, int(budget / max(time.perf_counter() - t0, 1e-5))))
+    times = {n: [] for n in graphs}
+    for t in range(trials + 1):
+        for n, gr in graphs.items():
+            gr.replay()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                gr.replay()
+            torch.cuda.synchronize()
+            if t:  # trial 0 warms every variant
+                times[n].append((time.perf_counter() - t0) / steps * 1e3)
+    res = {"steps_per_window": steps}
+    for n, v in times.items():
+        v = sorted(v)
+        res[n] = {"call_ms_median": round(v[len(v) // 2], 4), "call_ms_min": round(v[0], 4),
+                  "call_ms_max": round(v[-1], 4)}
+    return res
+
+
+def bench_encoder(m, x, which, trials, stream):
+    """(a) and (b) for one encoder `m` on the input x."""
+    instance = m.norm_fn == "instance"
+    res = {"norm": m.norm_fn, "B": x.shape[0], "convs": {}}
+    with torch.no_grad():
+        maps = {"layer1": F.relu(m.norm1(m.conv1(x)))}
+        maps["layer2"] = m.layer1(maps["layer1"])
+        maps["layer3"] = m.layer2(maps["layer2"])
+    for kind, (layer, blk, first) in KINDS.items():
+        block = getattr(m, layer)[blk]
+        if first:
+            with torch.no_grad():
+                src = maps[layer] if blk == 0 else getattr(m, layer)[0](maps[layer])
+                conv, norm = block.conv1, block.norm1
+                ref = F.relu(norm64(norm, conv64(conv, src)))
+            torch_fn = lambda: F.relu(norm(conv(src)))
+
+            def kernel_fn():
+                y, sc, sh = encoder._conv_norm("on", conv, norm, src, None, instance)
+                return y, sc, sh
+            check = lambda o: encoder._affine(*o)
+        else:
+            with torch.no_grad():
+                src = block.conv1(maps[layer])  # conv2's input before its norm
+            sc0 = 1.0 + 0.1 * torch.randn(src.shape[:2] if instance else src.shape[1:2], device=x.device)
+            sh0 = 0.1 * torch.randn_like(sc0)
+            skip = torch.randn_like(src)
+            conv, norm = block.conv2, block.norm2
+            view = (src.shape[0], src.shape[1], 1, 1) if instance else (1, src.shape[1], 1, 1)
+            act = F.relu(src * sc0.view(view) + sh0.view(view))  # what torch's conv2 reads (already stored there)
+            with torch.no_grad():
+                ref = F.relu(skip.double() + F.relu(norm64(norm, conv64(conv, act))))
+            torch_fn = lambda: F.relu(skip + F.relu(norm(conv(act))))
+
+            def kernel_fn():
+                y, sc, sh = encoder._conv_norm("on", conv, norm, src, (sc0, sh0), instance)
+                return _lib.enc_join(y, sc, sh, skip, out=y)
+            check = lambda o: o
+        gt, ot, kt = capture(torch_fn, stream)
+        gk, ok, kk = capture(kernel_fn, stream)
+        r = alternate({"torch": gt, "kernel": gk}, trials)
+        r["shape_in"] = list(src.shape)
+        r["cout"], r["stride"] = conv.out_channels, conv.stride[0]
+        with torch.no_grad():
+            r["kernel"]["rel_err_vs_fp64"] = norm_rel(check(ok), ref)
+            r["torch"]["rel_err_vs_fp64"] = norm_rel(ot, ref)
+        r["kernel_over_torch"] = round(r["kernel"]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
+        res["convs"][kind] = r
+        del gt, gk, kt, kk, ot, ok, ref
+        torch.cuda.empty_cache()
+
+    table = {k: v for k, v in encoder.USE_KERNEL.items() if k != "on"}
+    graphs, outs, keep = {}, {}, []
+    for vname, on, tab in (("torch", False, table), ("all", True, dict.fromkeys(table, True)), ("fused", True, table)):
+        BasicEncoder.fused = on
+        encoder.USE_KERNEL.update(tab)
+        graphs[vname], outs[vname], k = capture(lambda: m(x), stream)
+        keep.append(k)
+    BasicEncoder.fused = False
+    encoder.USE_KERNEL.update(table)
+    r = alternate(graphs, trials)
+    for vname in ("all", "fused"):
+        r[vname]["vs_torch_rel"] = norm_rel(outs[vname], outs["torch"])
+        r[f"{vname}_over_torch"] = round(r[vname]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
+    r["use_kernel"] = table
+    res["whole"] = r
+    del graphs, keep, outs
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_size(name, trials, dev):
+    pairs, C, H, W = SIZES[name]
+    torch.manual_seed(1234)
+    stream = torch.cuda.Stream()
+    res = {"input": [pairs, C, H, W]}
+    for which, norm, B in (("fnet", "instance", 2 * pairs), ("cnet", "batch", pairs)):
+        m = BasicEncoder(output_dim=256, norm_fn=norm, n_first_channels=C).to(dev).eval()
+        if norm == "batch":
+            with torch.no_grad():
+                for mod in m.modules():
+                    if isinstance(mod, torch.nn.BatchNorm2d):
+                        mod.running_mean.normal_(0.0, 0.1)
+                        mod.running_var.uniform_(0.5, 1.5)
+        x = torch.randn(B, C, H, W, device=dev) * (torch.rand(B, C, H, W, device=dev) < 0.15)
+        res[which] = bench_encoder(m, x, which, trials, stream)
+        del m, x
+        torch.cuda.empty_cache()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="dsec,b8,hires1920")
+    ap.add_argument("--trials", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_encoder needs an MI355X (no CPU fallback)")
+    if a.trials < 5:
+        sys.exit("--trials must be >= 5 (the median of at least 5 windows is reported)")
+    dev = torch.device("cuda", 0)
+    encoder.USE_KERNEL["on"] = True  # the key the single-convolution measurements run under
+    doc = {"device": torch.cuda.get_device_name(0),
+           "call": "one HIP graph per variant, variants alternated; convs: kernel launches vs the torch ops they "
+                   "replace; whole: BasicEncoder.forward",
+           "sizes": {n: bench_size(n, a.trials, dev) for n in a.sizes.split(",")}}
+    del encoder.USE_KERNEL["on"]
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
