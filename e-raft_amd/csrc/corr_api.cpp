@@ -729,6 +729,44 @@ int corr_convex_upsample(const float *flow, const float *mask, int N, int h, int
     return hip_status(launch_convex_upsample(flow, mask, N, h, w, out, (hipStream_t)stream), fn);
 }
 
+size_t corr_mask_upsample_weights_bytes(void) { return mask_upsample_weights_bytes(); }
+
+int corr_mask_upsample_pack_weights(const float *w, void *packed, void *stream) {
+    static const char *fn = "corr_mask_upsample_pack_weights";
+    g_err[0] = 0;
+    int rc;
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_mask_upsample_pack(w, packed, (hipStream_t)stream), fn);
+}
+
+int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                               const void *packed, const float *bias, float mask_scale, int B, int H, int W,
+                               float *out, void *stream) {
+    static const char *fn = "corr_mask_upsample_forward";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if (hidden_offset < 0 || (long long)hidden_offset + 256 > hidden_channels)
+        return fail(CORR_EINVAL, "%s: channels hidden_offset .. hidden_offset + 255 must lie in [0, hidden_channels) "
+                                 "(got hidden_offset = %d, hidden_channels = %d)",
+                    fn, hidden_offset, hidden_channels);
+    if ((rc = check_ptr(fn, hidden, "hidden")) || (rc = check_ptr(fn, flow, "flow")) ||
+        (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, bias, "bias")) ||
+        (rc = check_ptr(fn, out, "out")))
+        return rc;
+    if (!(mask_scale - mask_scale == 0.f)) return fail(CORR_EINVAL, "%s: mask_scale must be finite", fn);
+    const long double px = (long double)B * H * W * sizeof(float), ob = px * 128;
+    if (px * hidden_channels > (long double)(SIZE_MAX / 2) || ob > (long double)(SIZE_MAX / 2))
+        return fail(CORR_EINVAL, "%s: B*hidden_channels*H*W too large", fn);
+    if (ranges_overlap(out, ob, hidden, px * hidden_channels) || ranges_overlap(out, ob, flow, px * 2))
+        return fail(CORR_EINVAL, "%s: out must not overlap hidden or flow", fn);
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_mask_upsample(hidden, hidden_channels, hidden_offset, flow, packed, bias, mask_scale, B,
+                                           H, W, out, (hipStream_t)stream),
+                      fn);
+}
+
 size_t corr_convex_upsample_bwd_workspace(int N, int h, int w) {
     if (N < 1 || h < 1 || w < 1) return 0;
     return convex_upsample_bwd_workspace(N, h, w);

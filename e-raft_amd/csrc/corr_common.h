@@ -226,6 +226,13 @@ hipError_t launch_enc_finalize(const float *stats, int B, int C, int Ho, int Wo,
                                float *shift, hipStream_t s);
 hipError_t launch_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch,
                            const float *skip, int B, int C, int H, int W, float *out, hipStream_t s);
+// The mask head fused with the convex upsampling (corr_mask_upsample.hip): the weight pack, then
+// one launch from the hidden activations and the flow to the [B][2][8H][8W] prediction.
+size_t mask_upsample_weights_bytes();
+hipError_t launch_mask_upsample_pack(const float *w, void *packed, hipStream_t s);
+hipError_t launch_mask_upsample(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                                const void *packed, const float *bias, float mask_scale, int B, int H, int W,
+                                float *out, hipStream_t s);
 size_t build_bwd_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bwd(const float *grad_c, const float *f1, int NQ, const float *f2, int B,
                             int D, int H, int W, float *df1, float *df2, float *ws, hipStream_t s);

@@ -35,7 +35,8 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_ondemand_bwd_workspace", "corr_ondemand_backward", "corr_gru_weights_bytes",
            "corr_gru_pack_weights", "corr_gru_workspace", "corr_gru_half_step", "corr_conv_weights_bytes",
            "corr_conv_pack_weights", "corr_conv_forward", "corr_enc_stats_bytes", "corr_enc_conv_forward",
-           "corr_enc_norm_finalize", "corr_enc_join")
+           "corr_enc_norm_finalize", "corr_enc_join", "corr_mask_upsample_weights_bytes",
+           "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -157,7 +158,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_enc_conv_forward.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, sz, vp]
     lib.corr_enc_norm_finalize.argtypes = [vp, i, i, i, i, ctypes.c_float, vp, vp, vp]
     lib.corr_enc_join.argtypes = [vp, vp, vp, i, vp, i, i, i, i, vp, vp]
-    for f in ("corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
+    lib.corr_mask_upsample_weights_bytes.argtypes, lib.corr_mask_upsample_weights_bytes.restype = [], sz
+    lib.corr_mask_upsample_pack_weights.argtypes = [vp, vp, vp]
+    lib.corr_mask_upsample_forward.argtypes = [vp, i, i, vp, vp, vp, ctypes.c_float, i, i, i, vp, vp]
+    for f in ("corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
@@ -746,6 +750,59 @@ def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0):
     with torch.cuda.device(in_a.device):
         _check(lib.corr_conv_forward(ap, ca, bp, cb, B, H, W, pk, biasp, cout, int(bool(relu)), op, out.shape[1],
                                      out_offset, _stream(in_a)))
+    return out
+
+
+def mask_upsample_pack_weights(w):
+    """corr_mask_upsample_pack_weights: the mask head's 1x1 Conv2d weight [576, 256, 1, 1] (or
+    [576, 256]) -> the packed split (an opaque buffer)."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("w must be a torch.Tensor")
+    if tuple(w.shape) not in ((576, 256, 1, 1), (576, 256)):
+        raise ValueError(f"w must be [576, 256, 1, 1] (got {tuple(w.shape)})")
+    w = w.detach().float().contiguous()
+    wp = _dev(w, "w")
+    lib = load()
+    packed = torch.empty((lib.corr_mask_upsample_weights_bytes() + 3) // 4, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib.corr_mask_upsample_pack_weights(wp, packed.data_ptr(), _stream(w)))
+    return packed
+
+
+def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=None):
+    """corr_mask_upsample_forward: the convex upsampling of flow [B, 2, H, W] by the mask
+    scale * (W hidden[:, hidden_offset:hidden_offset + 256] + bias), with the pack of
+    mask_upsample_pack_weights and bias [576] -> out [B, 2, 8H, 8W] (allocated when None).  The
+    mask itself is never stored.  Returns `out`."""
+    hp = _dev(hidden, "hidden")
+    if hidden.dim() != 4:
+        raise ValueError(f"hidden must be [B, C, H, W] (got {tuple(hidden.shape)})")
+    B, hc, H, W = hidden.shape
+    hidden_offset = int(hidden_offset)
+    if hidden_offset < 0 or hidden_offset + 256 > hc:
+        raise ValueError(f"hidden {tuple(hidden.shape)} does not hold channels {hidden_offset} .. "
+                         f"{hidden_offset + 255}")
+    fp = _dev(flow, "flow")
+    if tuple(flow.shape) != (B, 2, H, W) or flow.device != hidden.device:
+        raise ValueError(f"flow must be [{B}, 2, {H}, {W}] on {hidden.device} (got {tuple(flow.shape)} on "
+                         f"{flow.device})")
+    lib = load()
+    need = lib.corr_mask_upsample_weights_bytes()
+    pk = _dev(packed, "packed")
+    if packed.numel() * 4 < need or packed.device != hidden.device:
+        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the mask head needs "
+                         f"{need} on {hidden.device}")
+    bp = _dev(bias, "bias")
+    if bias.numel() != 576 or bias.device != hidden.device:
+        raise ValueError(f"bias must hold 576 values on {hidden.device} (got {tuple(bias.shape)})")
+    if out is None:
+        out = torch.empty((B, 2, 8 * H, 8 * W), dtype=torch.float32, device=hidden.device)
+    op = _dev(out, "out")
+    if tuple(out.shape) != (B, 2, 8 * H, 8 * W) or out.device != hidden.device:
+        raise ValueError(f"out must be [{B}, 2, {8 * H}, {8 * W}] on {hidden.device} (got {tuple(out.shape)})")
+    with torch.cuda.device(hidden.device):
+        _check(lib.corr_mask_upsample_forward(hp, hc, hidden_offset, fp, pk, bp, float(scale), B, H, W, op,
+                                              _stream(hidden)))
     return out
 
 

@@ -243,12 +243,17 @@ class BasicUpdateBlock(nn.Module):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in (*ts, *ps)))
 
-    def forward(self, net, inp, corr, flow, fused=False):
+    def forward(self, net, inp, corr, flow, fused=False, defer_mask=False):
+        """Returns (net, mask, delta_flow).  With `defer_mask`: (net, hidden, delta_flow), hidden =
+        relu(mask[0](net)) [B, 256, H, W], and mask[2] with its 0.25 is left to the caller
+        (upsample.mask_upsample)."""
         if self.fused and self._fusable(net, inp, corr, flow, fused):
             from .update import update_block
-            return update_block(self, net, inp, corr, flow, fused)
+            return update_block(self, net, inp, corr, flow, fused, defer_mask=defer_mask)
         motion = self.encoder(flow, corr, fused)
         net = self.gru(net, torch.cat([inp, motion], dim=1))
+        if defer_mask:
+            return net, self.mask[1](self.mask[0](net)), self.flow_head(net)
         return net, 0.25 * self.mask(net), self.flow_head(net)
 
 
@@ -306,6 +311,11 @@ class ERAFT(nn.Module):
     # corr_lookup_conv_bwd); ERAFT_AMD_FUSE_CONV=0 keeps lookup + MIOpen convc1.  DSEC: 20.1 vs
     # 38.9 us per GRU iteration (profiles/r04k_conv_fwd_bwd_timing.jsonl)
     fuse_lookup_conv = os.environ.get("ERAFT_AMD_FUSE_CONV", "1") == "1"
+    # ERAFT_AMD_FUSE_UPSAMPLE=1: at inference on the MI355X the mask head's 1x1 convolution, its
+    # 0.25, the softmax over the taps and the convex combination are one corr_mask_upsample_forward
+    # launch per iteration (upsample.py) and the 576-channel mask is never stored.  Default off
+    # (DESIGN §17 has the measurements); training always runs the torch code.
+    fuse_mask_upsample = os.environ.get("ERAFT_AMD_FUSE_UPSAMPLE", "0") == "1"
 
     def __init__(self, config, n_first_channels):
         super().__init__()
@@ -345,6 +355,19 @@ class ERAFT(nn.Module):
         up = torch.sum(mask * up, dim=2).permute(0, 1, 4, 2, 5, 3)
         return up.reshape(n, 2, 8 * h, 8 * w)
 
+    def _mask_fusable(self, *ts):
+        """upsample.mask_upsample is built for fp32 GPU tensors and the reference's mask head
+        (256 -> 576, 1x1, with a bias), and has no backward."""
+        head = self.update_block.mask[2]
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.device == ts[0].device for t in ts):
+            return False
+        if tuple(head.weight.shape) != (576, 256, 1, 1) or head.bias is None:
+            return False
+        ps = list(self.update_block.parameters())
+        if any(p.dtype != torch.float32 or p.device != ts[0].device for p in ps):
+            return False
+        return not (torch.is_grad_enabled() and any(t.requires_grad for t in (*ts, *self.parameters())))
+
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True):
         image1 = self.image_padder.pad(image1).contiguous()
         image2 = self.image_padder.pad(image2).contiguous()
@@ -373,7 +396,15 @@ class ERAFT(nn.Module):
                 corr = corr_fn.lookup_conv(coords1, enc.convc1.weight, enc.convc1.bias)
             else:
                 corr = corr_fn(coords1)
-            net, up_mask, delta = self.update_block(net, inp, corr, coords1 - coords0, fuse)
-            coords1 = coords1 + delta
-            predictions.append(self.image_padder.unpad(self.upsample_flow(coords1 - coords0, up_mask)))
+            if self.fuse_mask_upsample and self._mask_fusable(net, inp, corr, coords1):
+                from .upsample import channel_window, mask_upsample
+                net, hidden, delta = self.update_block(net, inp, corr, coords1 - coords0, fuse, defer_mask=True)
+                coords1 = coords1 + delta
+                hidden, off = channel_window(hidden)
+                up = mask_upsample(self.update_block.mask[2], hidden, off, coords1 - coords0)
+            else:
+                net, up_mask, delta = self.update_block(net, inp, corr, coords1 - coords0, fuse)
+                coords1 = coords1 + delta
+                up = self.upsample_flow(coords1 - coords0, up_mask)
+            predictions.append(self.image_padder.unpad(up))
         return coords1 - coords0, predictions

@@ -54,10 +54,13 @@ def _conv(name, convs, x, out, off):
             off += c.out_channels
 
 
-def update_block(module, net, inp, corr, flow, fused=False):
+def update_block(module, net, inp, corr, flow, fused=False, defer_mask=False):
     """BasicUpdateBlock.forward (update.py:85-107) for `module`: net, inp [B, 128, H, W], corr the
     lookup [B, 324, H, W] (or relu(convc1(lookup)) [B, 256, H, W] when `fused`), flow
-    [B, 2, H, W]; fp32 on the GPU.  Returns (net, mask, delta_flow)."""
+    [B, 2, H, W]; fp32 on the GPU.  Returns (net, mask, delta_flow); with `defer_mask`
+    (net, hidden, delta_flow), where hidden = relu(mask[0](net)) is the view of channels 256 .. 511
+    of the stacked heads' buffer (hidden._base is that buffer, so upsample.mask_upsample reads it
+    in place at offset 256) and mask[2] is left to the caller."""
     for t, nm in ((net, "net"), (inp, "inp"), (corr, "corr"), (flow, "flow")):
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
             raise RuntimeError(f"{nm} must be a tensor on an MI355X (HIP) device: eraft_amd has no CPU fallback")
@@ -75,4 +78,6 @@ def update_block(module, net, inp, corr, flow, fused=False):
     net = module.gru(net.contiguous(), x)
     hd = torch.empty((B, 512, H, W), dtype=torch.float32, device=net.device)  # [flow_head.conv1 | mask[0]]
     _conv("heads", (module.flow_head.conv1, module.mask[0]), net.contiguous(), hd, 0)
+    if defer_mask:
+        return net, hd[:, 256:], module.flow_head.conv2(hd[:, :256])
     return net, 0.25 * module.mask[2](hd[:, 256:]), module.flow_head.conv2(hd[:, :256])

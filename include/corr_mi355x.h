@@ -66,7 +66,8 @@ extern "C" {
  *        has NaN) instead of NaN for every output an infinity reaches.
  *        Added under 202 (purely additive, no version change): corr_ondemand_workspace,
  *        corr_ondemand_prepare, corr_ondemand_lookup; corr_ondemand_bwd_workspace,
- *        corr_ondemand_backward. */
+ *        corr_ondemand_backward; corr_mask_upsample_weights_bytes,
+ *        corr_mask_upsample_pack_weights, corr_mask_upsample_forward. */
 int corr_version(void);
 
 /* Thread-local description of the last error on this thread ("" if none). */
@@ -592,6 +593,41 @@ int corr_enc_norm_finalize(const void *stats, int B, int C, int Ho, int Wo, floa
                            float *shift, void *stream);
 int corr_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch,
                   const float *skip, int B, int C, int H, int W, float *out, void *stream);
+
+/*
+ * The update block's mask head fused with the convex upsampling (model/update.py:99-107: the
+ * 256 -> 576 1x1 convolution mask[2] and its 0.25; model/eraft.py:75-86 upsample_flow), inference
+ * only: one launch from the hidden activations relu(mask[0](net)) and the 1/8-resolution flow to
+ * the full-resolution prediction.  The [B][576][H][W] mask is never stored.
+ *   logit[k][i][j] = mask_scale * (bias[64k + 8i + j] + sum_c w[64k + 8i + j][c] * hidden[n][hidden_offset + c][y][x])
+ *   p = softmax of logit over the 9 taps k (max-subtracted, summed in tap order k = 0..8)
+ *   out[n][ch][8y + i][8x + j] = sum_k p[k] * 8 * flow[n][ch][y + k/3 - 1][x + k%3 - 1]
+ * for c < 256, i, j < 8, ch < 2; a flow neighbour outside the map counts as 0.  The softmax and
+ * the combination are corr_convex_upsample's, op for op.
+ * Input: hidden is a [B][hidden_channels][H][W] tensor of which channels hidden_offset ..
+ * hidden_offset + 255 are read in place (the mask half of the update block's stacked heads
+ * buffer needs no copy); flow is [B][2][H][W]; out is [B][2][8H][8W], every float of it written
+ * and nothing else; out's byte range must not overlap hidden's or flow's.
+ * Weights: w is the contiguous Conv2d weight [576][256] (a [576][256][1][1] tensor).  It is split
+ * once per weight version by corr_mask_upsample_pack_weights into a
+ * corr_mask_upsample_weights_bytes() buffer (16-B aligned, opaque).  bias is [576].  All tensors
+ * fp32, 4-byte aligned (a 16-byte aligned out takes 16-byte stores).
+ * Arithmetic: the logits are an implicit GEMM with K = 256 on the bf16 MFMA with
+ * CORR_BUILD_BF16X6's exact three-piece split (six products per fp32 product, no scales: no
+ * narrower than fp32), fp32 accumulation in ascending 32-channel steps, then + bias and
+ * * mask_scale, each fp32 op rounded once; deterministic.  Non-finite inputs are NOT
+ * parity-checked.
+ * CORR_EINVAL: a NULL hidden, flow, packed, bias or out; B, H or W < 1 or B*H*W >= 2^31;
+ * hidden_offset < 0 or hidden_offset + 256 > hidden_channels; packed not 16-byte aligned; a
+ * mask_scale that is not finite; out overlapping hidden or flow.  Every refusal comes before any
+ * HIP call.  No workspace, no allocation, no synchronisation; the launch goes on `stream` and can
+ * be captured into a graph.
+ */
+size_t corr_mask_upsample_weights_bytes(void);
+int corr_mask_upsample_pack_weights(const float *w, void *packed, void *stream);
+int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                               const void *packed, const float *bias, float mask_scale, int B, int H, int W,
+                               float *out, void *stream);
 
 #ifdef __cplusplus
 }
