@@ -718,6 +718,128 @@ int corr_enc_join(const float *y, const float *scale, const float *shift, int no
                       fn);
 }
 
+size_t corr_enc_stem_weights_bytes(int cout, int cin) {
+    if (!enc_stem_supported(cout, cin)) return 0;
+    return enc_stem_weights_bytes(cout);
+}
+
+static int check_stem_channels(const char *fn, int cout, int cin) {
+    if (cin < 1) return fail(CORR_EINVAL, "%s: cin must be >= 1 (got %d)", fn, cin);
+    if (!enc_stem_supported(cout, cin))
+        return fail(CORR_EUNSUPPORTED, "%s: built for 1 <= cin <= 16 and 1 <= cout <= 1024 (got cin = %d, cout = %d)",
+                    fn, cin, cout);
+    return CORR_OK;
+}
+
+int corr_enc_stem_pack_weights(const float *w, int cout, int cin, void *packed, void *stream) {
+    static const char *fn = "corr_enc_stem_pack_weights";
+    g_err[0] = 0;
+    int rc;
+    if ((rc = check_stem_channels(fn, cout, cin))) return rc;
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_enc_stem_pack(w, cout, cin, packed, (hipStream_t)stream), fn);
+}
+
+// The checks the stem and the pointwise convolution share, after their channel counts: the
+// pointers, the statistics buffer, the pack's alignment, out against in.
+static int check_enc_front(const char *fn, const float *in, int cin, int B, int H, int W, int stride,
+                           const void *packed, const float *bias, int cout, const float *out, const void *stats,
+                           size_t stats_bytes) {
+    int rc;
+    if ((rc = check_ptr(fn, in, "in")) || (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, out, "out")))
+        return rc;
+    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    if (stats) {
+        if ((rc = check_ptr(fn, stats, "stats"))) return rc;
+        const size_t need = enc_stats_bytes(B, cout, Ho, Wo);
+        if (stats_bytes < need)
+            return fail(CORR_EINVAL, "%s: stats of %zu bytes needed, got %zu", fn, need, stats_bytes);
+    }
+    const long double ib = (long double)B * H * W * sizeof(float) * cin;
+    const long double ob = (long double)B * Ho * Wo * sizeof(float) * cout;
+    if (ranges_overlap(out, ob, in, ib)) return fail(CORR_EINVAL, "%s: out must not overlap in", fn);
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return CORR_OK;
+}
+
+int corr_enc_stem_forward(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
+                          int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
+    static const char *fn = "corr_enc_stem_forward";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    if ((rc = check_stem_channels(fn, cout, cin))) return rc;
+    if ((rc = check_enc_front(fn, in, cin, B, H, W, 2, packed, bias, cout, out, stats, stats_bytes))) return rc;
+    return hip_status(launch_enc_stem(in, cin, B, H, W, packed, bias, cout, out, static_cast<float *>(stats),
+                                      (hipStream_t)stream),
+                      fn);
+}
+
+static int check_pw_channels(const char *fn, int cout, int cin) {
+    if (!enc_pw_supported(cout, cin))
+        return fail(CORR_EUNSUPPORTED,
+                    "%s: built for 1 <= cout <= 1024 and cin a multiple of 32 in 32 .. 1024 (got cout = %d, cin = %d)",
+                    fn, cout, cin);
+    return CORR_OK;
+}
+
+size_t corr_enc_pw_weights_bytes(int cout, int cin) {
+    if (!enc_pw_supported(cout, cin)) return 0;
+    return enc_pw_weights_bytes(cout, cin);
+}
+
+int corr_enc_pw_pack_weights(const float *w, int cout, int cin, void *packed, void *stream) {
+    static const char *fn = "corr_enc_pw_pack_weights";
+    g_err[0] = 0;
+    int rc;
+    if ((rc = check_pw_channels(fn, cout, cin))) return rc;
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_enc_pw_pack(w, cout, cin, packed, (hipStream_t)stream), fn);
+}
+
+int corr_enc_pw_forward(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
+                        const float *bias, int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
+    static const char *fn = "corr_enc_pw_forward";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    if (stride != 1 && stride != 2)
+        return fail(CORR_EUNSUPPORTED, "%s: built for stride 1 and 2 (got %d)", fn, stride);
+    if ((rc = check_pw_channels(fn, cout, cin))) return rc;
+    if ((rc = check_enc_front(fn, in, cin, B, H, W, stride, packed, bias, cout, out, stats, stats_bytes))) return rc;
+    return hip_status(launch_enc_pw(in, cin, B, H, W, stride, packed, bias, cout, out, static_cast<float *>(stats),
+                                    (hipStream_t)stream),
+                      fn);
+}
+
+int corr_enc_join_affine(const float *y, const float *scale, const float *shift, int norm_per_batch,
+                         const float *skip, const float *skip_scale, const float *skip_shift, int skip_per_batch,
+                         int skip_relu, int B, int C, int H, int W, float *out, void *stream) {
+    static const char *fn = "corr_enc_join_affine";
+    g_err[0] = 0;
+    int rc = check_enc_planes(fn, B, C, H, W);
+    if (rc) return rc;
+    if ((rc = check_ptr(fn, y, "y")) || (rc = check_ptr(fn, scale, "scale")) || (rc = check_ptr(fn, shift, "shift")) ||
+        (rc = check_ptr(fn, skip, "skip")) || (rc = check_ptr(fn, out, "out")))
+        return rc;
+    if (!skip_scale != !skip_shift)
+        return fail(CORR_EINVAL, "%s: skip_scale and skip_shift must both be given or both be NULL", fn);
+    if (skip_scale && ((rc = check_ptr(fn, skip_scale, "skip_scale")) || (rc = check_ptr(fn, skip_shift, "skip_shift"))))
+        return rc;
+    for (const int f : {norm_per_batch, skip_per_batch, skip_relu})
+        if (f != 0 && f != 1)
+            return fail(CORR_EINVAL, "%s: norm_per_batch, skip_per_batch and skip_relu must be 0 or 1 (got %d, %d, %d)",
+                        fn, norm_per_batch, skip_per_batch, skip_relu);
+    return hip_status(launch_enc_join_affine(y, scale, shift, norm_per_batch, skip, skip_scale, skip_shift,
+                                             skip_per_batch, skip_relu, B, C, H, W, out, (hipStream_t)stream),
+                      fn);
+}
+
 int corr_convex_upsample(const float *flow, const float *mask, int N, int h, int w, float *out, void *stream) {
     static const char *fn = "corr_convex_upsample";
     g_err[0] = 0;

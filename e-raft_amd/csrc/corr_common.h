@@ -226,6 +226,23 @@ hipError_t launch_enc_finalize(const float *stats, int B, int C, int Ho, int Wo,
                                float *shift, hipStream_t s);
 hipError_t launch_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch,
                            const float *skip, int B, int C, int H, int W, float *out, hipStream_t s);
+// The encoders around their residual stages (corr_enc_front.hip): the 7x7 stride-2 stem, the 1x1
+// convolution at stride 1 or 2 (both with the optional per-tile statistics of launch_enc_conv),
+// and the join whose skip takes an affine (and a ReLU) of its own (skip_scale null: none).
+bool enc_stem_supported(int cout, int cin);
+size_t enc_stem_weights_bytes(int cout);
+hipError_t launch_enc_stem_pack(const float *w, int cout, int cin, void *packed, hipStream_t s);
+hipError_t launch_enc_stem(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
+                           int cout, float *out, float *stats, hipStream_t s);
+bool enc_pw_supported(int cout, int cin);
+size_t enc_pw_weights_bytes(int cout, int cin);
+hipError_t launch_enc_pw_pack(const float *w, int cout, int cin, void *packed, hipStream_t s);
+hipError_t launch_enc_pw(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
+                         const float *bias, int cout, float *out, float *stats, hipStream_t s);
+hipError_t launch_enc_join_affine(const float *y, const float *scale, const float *shift, int norm_per_batch,
+                                  const float *skip, const float *skip_scale, const float *skip_shift,
+                                  int skip_per_batch, int skip_relu, int B, int C, int H, int W, float *out,
+                                  hipStream_t s);
 // The mask head fused with the convex upsampling (corr_mask_upsample.hip): the weight pack, then
 // one launch from the hidden activations and the flow to the [B][2][8H][8W] prediction.
 size_t mask_upsample_weights_bytes();

@@ -36,7 +36,9 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_gru_pack_weights", "corr_gru_workspace", "corr_gru_half_step", "corr_conv_weights_bytes",
            "corr_conv_pack_weights", "corr_conv_forward", "corr_enc_stats_bytes", "corr_enc_conv_forward",
            "corr_enc_norm_finalize", "corr_enc_join", "corr_mask_upsample_weights_bytes",
-           "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward")
+           "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_stem_weights_bytes",
+           "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_weights_bytes",
+           "corr_enc_pw_pack_weights", "corr_enc_pw_forward", "corr_enc_join_affine")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -158,10 +160,18 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_enc_conv_forward.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, sz, vp]
     lib.corr_enc_norm_finalize.argtypes = [vp, i, i, i, i, ctypes.c_float, vp, vp, vp]
     lib.corr_enc_join.argtypes = [vp, vp, vp, i, vp, i, i, i, i, vp, vp]
+    lib.corr_enc_stem_weights_bytes.argtypes, lib.corr_enc_stem_weights_bytes.restype = [i, i], sz
+    lib.corr_enc_stem_pack_weights.argtypes = [vp, i, i, vp, vp]
+    lib.corr_enc_stem_forward.argtypes = [vp, i, i, i, i, vp, vp, i, vp, vp, sz, vp]
+    lib.corr_enc_pw_weights_bytes.argtypes, lib.corr_enc_pw_weights_bytes.restype = [i, i], sz
+    lib.corr_enc_pw_pack_weights.argtypes = [vp, i, i, vp, vp]
+    lib.corr_enc_pw_forward.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, sz, vp]
+    lib.corr_enc_join_affine.argtypes = [vp, vp, vp, i, vp, vp, vp, i, i, i, i, i, i, vp, vp]
     lib.corr_mask_upsample_weights_bytes.argtypes, lib.corr_mask_upsample_weights_bytes.restype = [], sz
     lib.corr_mask_upsample_pack_weights.argtypes = [vp, vp, vp]
     lib.corr_mask_upsample_forward.argtypes = [vp, i, i, vp, vp, vp, ctypes.c_float, i, i, i, vp, vp]
-    for f in ("corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
+    for f in ("corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
+              "corr_enc_join_affine", "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
@@ -886,4 +896,108 @@ def enc_join(y, scale, shift, skip, out=None):
         raise ValueError(f"out {tuple(out.shape)} does not match y {tuple(y.shape)}")
     with torch.cuda.device(y.device):
         _check(load().corr_enc_join(yp, sp, hp, nb, kp, B, C, H, W, op, _stream(y)))
+    return out
+
+
+def _enc_front_pack(w, k, name):
+    """A [cout, cin, k, k] (k = 1: or [cout, cin]) weight -> its packed split."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("w must be a torch.Tensor")
+    if not (w.dim() == 4 and tuple(w.shape[2:]) == (k, k)) and not (k == 1 and w.dim() == 2):
+        raise ValueError(f"w must be [cout, cin, {k}, {k}] (got {tuple(w.shape)})")
+    w = w.detach().float().contiguous()
+    cout, cin = w.shape[0], w.shape[1]
+    wp = _dev(w, "w")
+    lib = load()
+    n = getattr(lib, f"corr_enc_{name}_weights_bytes")(cout, cin)
+    if n == 0:
+        raise CorrError(CORR_EUNSUPPORTED, f"corr_enc_{name}_weights_bytes: unsupported cout = {cout}, cin = {cin}")
+    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(getattr(lib, f"corr_enc_{name}_pack_weights")(wp, cout, cin, packed.data_ptr(), _stream(w)))
+    return packed
+
+
+def enc_stem_pack_weights(w):
+    """corr_enc_stem_pack_weights: the stem's Conv2d weight [cout, cin, 7, 7], cin <= 16 -> the
+    packed split (an opaque buffer)."""
+    return _enc_front_pack(w, 7, "stem")
+
+
+def enc_pw_pack_weights(w):
+    """corr_enc_pw_pack_weights: a 1x1 Conv2d weight [cout, cin, 1, 1] (or [cout, cin]) -> the
+    packed split (an opaque buffer)."""
+    return _enc_front_pack(w, 1, "pw")
+
+
+def _enc_front_forward(name, x, packed, bias, cout, stride, stats):
+    xp = _dev(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, cin, H, W] (got {tuple(x.shape)})")
+    B, cin, H, W = x.shape
+    lib = load()
+    need = getattr(lib, f"corr_enc_{name}_weights_bytes")(cout, cin)
+    if need == 0 or stride not in (1, 2):
+        raise CorrError(CORR_EUNSUPPORTED,
+                        f"corr_enc_{name}_forward: unsupported cout = {cout}, cin = {cin}, stride = {stride}")
+    pk = _dev(packed, "packed")
+    if packed.numel() * 4 < need or packed.device != x.device:
+        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
+                         f"{need} on {x.device}")
+    biasp = None
+    if bias is not None:
+        biasp = _dev(bias, "bias")
+        if bias.numel() != cout or bias.device != x.device:
+            raise ValueError(f"bias must hold cout = {cout} values on {x.device} (got {tuple(bias.shape)})")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    out = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    st, nst = None, 0
+    if stats:
+        nst = lib.corr_enc_stats_bytes(B, cout, Ho, Wo)
+        st = torch.empty(nst // 4, dtype=torch.float32, device=x.device)
+    stp = None if st is None else st.data_ptr()
+    with torch.cuda.device(x.device):
+        if name == "stem":
+            _check(lib.corr_enc_stem_forward(xp, cin, B, H, W, pk, biasp, cout, out.data_ptr(), stp, nst, _stream(x)))
+        else:
+            _check(lib.corr_enc_pw_forward(xp, cin, B, H, W, stride, pk, biasp, cout, out.data_ptr(), stp, nst,
+                                           _stream(x)))
+    return (out, st) if stats else out
+
+
+def enc_stem_forward(x, packed, bias, cout, stats=False):
+    """corr_enc_stem_forward: the 7x7 convolution (stride 2, padding 3, + bias, no ReLU) of
+    x [B, cin, H, W], cin <= 16, with the pack of enc_stem_pack_weights.  Returns out
+    [B, cout, Ho, Wo], or (out, stats) with the per-tile statistics for enc_norm_finalize."""
+    return _enc_front_forward("stem", x, packed, bias, cout, 2, stats)
+
+
+def enc_pw_forward(x, packed, bias, cout, stride=1, stats=False):
+    """corr_enc_pw_forward: the 1x1 convolution (stride 1 or 2, + bias, no ReLU) of
+    x [B, cin, H, W] with the pack of enc_pw_pack_weights.  Returns out [B, cout, Ho, Wo], or
+    (out, stats) with the per-tile statistics for enc_norm_finalize."""
+    return _enc_front_forward("pw", x, packed, bias, cout, stride, stats)
+
+
+def enc_join_affine(y, scale, shift, skip, skip_scale=None, skip_shift=None, skip_relu=False, out=None):
+    """corr_enc_join_affine: relu(s(skip) + relu(y * scale + shift)) with s(v) = v * skip_scale +
+    skip_shift (v itself when the pair is None), followed by a ReLU when `skip_relu`; y, skip
+    [B, C, H, W], each pair [B, C] or [C]; into `out` (which may be y; allocated when None)."""
+    yp, kp = _dev(y, "y"), _dev(skip, "skip")
+    if y.dim() != 4 or skip.shape != y.shape or skip.device != y.device:
+        raise ValueError(f"y and skip must be equal [B, C, H, W] tensors on one device "
+                         f"(got {tuple(y.shape)}, {tuple(skip.shape)})")
+    B, C, H, W = y.shape
+    sp, hp, nb = _enc_norm(scale, shift, B, C, y.device, "norm")
+    if (skip_scale is None) != (skip_shift is None):
+        raise ValueError("skip_scale and skip_shift must both be given or both be None")
+    ksp, khp, knb = (None, None, 0) if skip_scale is None else _enc_norm(skip_scale, skip_shift, B, C, y.device, "skip")
+    if out is None:
+        out = torch.empty_like(y)
+    op = _dev(out, "out")
+    if out.shape != y.shape or out.device != y.device:
+        raise ValueError(f"out {tuple(out.shape)} does not match y {tuple(y.shape)}")
+    with torch.cuda.device(y.device):
+        _check(load().corr_enc_join_affine(yp, sp, hp, nb, kp, ksp, khp, knb, int(bool(skip_relu)), B, C, H, W, op,
+                                           _stream(y)))
     return out

@@ -1,12 +1,15 @@
-"""BasicEncoder's residual stages on the MI355X: each ResidualBlock's two 3x3 convolutions as
-corr_enc_conv_forward launches (csrc/corr_conv.hip: bf16 MFMA with the exact three-piece split, at
-stride 1 or 2).  The norm between two convolutions is never applied to a stored map: the producer
-leaves per-tile statistics, corr_enc_norm_finalize turns them into a per-(b, c) scale and shift,
-and the consumer normalises (and applies the ReLU) while it stages its input; corr_enc_join does
-the same for the block's output and adds the skip.  An eval-mode batch norm brings its scale and
-shift from its running statistics instead.  The 7x7 stem, the 1x1 head and the strided blocks'
-1x1 projections stay on torch.  Inference only: there is no backward, so model.BasicEncoder takes
-this path only when autograd is not recording.
+"""BasicEncoder on the MI355X: each ResidualBlock's two 3x3 convolutions as corr_enc_conv_forward
+launches (csrc/corr_conv.hip: bf16 MFMA with the exact three-piece split, at stride 1 or 2), the
+7x7 stem as corr_enc_stem_forward and the strided blocks' 1x1 projections and the 1x1 head as
+corr_enc_pw_forward (csrc/corr_enc_front.hip, the same arithmetic).  A norm is never applied to a
+stored map: the producer leaves per-tile statistics, corr_enc_norm_finalize turns them into a
+per-(b, c) scale and shift, and the consumer normalises (and applies the ReLU) while it stages its
+input; corr_enc_join does the same for the block's output and adds the skip, and
+corr_enc_join_affine also normalises that skip (the raw stem map with its ReLU, the raw projection
+without one).  An eval-mode batch norm brings its scale and shift from its running statistics
+instead.  USE_KERNEL says which pieces take a kernel; the others run on torch as they always did.
+Inference only: there is no backward, so model.BasicEncoder takes this path only when autograd is
+not recording.
 """
 from __future__ import annotations
 
@@ -18,12 +21,17 @@ import torch.nn.functional as F
 from . import _lib
 from .update import _conv_pack
 
-# Which convolutions take the HIP kernel under the switch, per stage and stride (each is
-# judged on its own against the torch ops it replaces, conv + norm + ReLU, at both DSEC encoder
-# batch sizes).  One that is False runs on MIOpen with the torch norm.
-USE_KERNEL = {"layer1": True, "layer2.s2": True, "layer2": True, "layer3.s2": True, "layer3": True}
+# Which pieces take the HIP kernel under the switch (each is judged on its own
+# against the torch ops it replaces at both DSEC encoder batch sizes: a 3x3 convolution against
+# conv + norm + ReLU, the stem likewise, a projection against conv + norm, the head against the
+# conv).  One that is False runs on MIOpen / rocBLAS with the torch norm and a stored map.
+USE_KERNEL = {"layer1": True, "layer2.s2": True, "layer2": True, "layer3.s2": True, "layer3": True,
+              "stem": True, "layer2.proj": True, "layer3.proj": True, "head": True}
+
+STEM_MAX_CIN = 16  # corr_enc_stem_forward's bound; a wider stem runs on torch (the stem alone)
 
 _BN_AFFINE = {}  # ids of a BatchNorm2d's tensors -> (weakrefs to them, their (data_ptr, _version)s, scale, shift)
+_FRONT_PACKS = {}  # ids of a conv's weight and bias -> (weakrefs to them, their (data_ptr, _version)s, pack, bias)
 
 
 def _bn_affine(norm):
@@ -51,10 +59,36 @@ def _bn_affine(norm):
     return ent[2], ent[3]
 
 
+def _front_pack(conv, pack):
+    """(pack, bias) of the stem or a 1x1 Conv2d, made by `pack` (_lib.enc_stem_pack_weights or
+    _lib.enc_pw_pack_weights) and cached with update._conv_pack's scheme: keyed by the parameters'
+    ids, held by weak references, together with the (data_ptr, _version)s they were made from."""
+    ts = (conv.weight, conv.bias)
+    ids = tuple(id(t) for t in ts)
+    key = tuple((t.data_ptr(), t._version) for t in ts)
+    ent = _FRONT_PACKS.get(ids)
+    if ent is None or any(r() is not t for r, t in zip(ent[0], ts)) or ent[1] != key:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("encoder_forward: the convolution weights must be packed before a graph capture "
+                               "(run one forward outside the capture first)")
+        drop = lambda _r, ids=ids: _FRONT_PACKS.pop(ids, None)
+        ent = (tuple(weakref.ref(t, drop) for t in ts), key, pack(conv.weight), conv.bias.detach().float().contiguous())
+        _FRONT_PACKS[ids] = ent
+    return ent[2], ent[3]
+
+
 def _affine(y, scale, shift):
     """relu(y * scale + shift) on torch, scale and shift [B, C] or [C]."""
     v = (y.shape[0], y.shape[1], 1, 1) if scale.dim() == 2 else (1, y.shape[1], 1, 1)
     return F.relu(y * scale.view(v) + shift.view(v))
+
+
+def _norm_of(y, st, norm, instance):
+    """(scale, shift) of `norm` on the kernel output y: from its statistics st (instance norm) or
+    from the batch norm's running statistics."""
+    if not instance:
+        return _bn_affine(norm)
+    return _lib.enc_norm_finalize(st, y.shape[0], y.shape[1], y.shape[2], y.shape[3], norm.eps)
 
 
 def _conv_norm(key, conv, norm, x, in_norm, instance):
@@ -68,18 +102,35 @@ def _conv_norm(key, conv, norm, x, in_norm, instance):
     if not instance:
         return (_lib.enc_conv_forward(x, packed, bias, conv.out_channels, conv.stride[0], sc, sh), *_bn_affine(norm))
     y, st = _lib.enc_conv_forward(x, packed, bias, conv.out_channels, conv.stride[0], sc, sh, stats=True)
-    return (y, *_lib.enc_norm_finalize(st, y.shape[0], y.shape[1], y.shape[2], y.shape[3], norm.eps))
+    return (y, *_norm_of(y, st, norm, True))
 
 
-def _block(name, block, x, instance):
-    """ResidualBlock.forward (extractor.py:43-52) for `block`."""
+def _pw(conv, x, stats=False):
+    """conv(x) for a 1x1 Conv2d on the pointwise kernel (with the statistics when asked)."""
+    packed, bias = _front_pack(conv, _lib.enc_pw_pack_weights)
+    return _lib.enc_pw_forward(x, packed, bias, conv.out_channels, conv.stride[0], stats=stats)
+
+
+def _block(name, block, x, x_norm, instance):
+    """ResidualBlock.forward (extractor.py:43-52) for `block` on relu(x * x_norm[0] + x_norm[1])
+    (the raw stem map and its norm), or on x when x_norm is None."""
     s2 = block.downsample is not None
-    y, sc, sh = _conv_norm(name + ".s2" if s2 else name, block.conv1, block.norm1, x, None, instance)
+    y, sc, sh = _conv_norm(name + ".s2" if s2 else name, block.conv1, block.norm1, x, x_norm, instance)
     y, sc, sh = _conv_norm(name, block.conv2, block.norm2, y, None if sc is None else (sc, sh), instance)
-    skip = (block.downsample(x) if s2 else x).contiguous()
-    if sc is None:
-        return F.relu(skip + y)
-    return _lib.enc_join(y, sc, sh, skip, out=y)
+    if sc is None:  # conv2 ran on torch: y is normalised already, the join is torch's
+        if x_norm is not None:
+            x = _affine(x, *x_norm)
+        return F.relu((block.downsample(x) if s2 else x) + y)
+    if s2 and USE_KERNEL[name + ".proj"]:
+        conv, norm = block.downsample[0], block.downsample[1]
+        p = _pw(conv, x, stats=instance)
+        p, st = p if instance else (p, None)
+        return _lib.enc_join_affine(y, sc, sh, p, *_norm_of(p, st, norm, instance), skip_relu=False, out=y)
+    if s2:
+        return _lib.enc_join(y, sc, sh, block.downsample(x).contiguous(), out=y)
+    if x_norm is not None:
+        return _lib.enc_join_affine(y, sc, sh, x, *x_norm, skip_relu=True, out=y)
+    return _lib.enc_join(y, sc, sh, x, out=y)
 
 
 def encoder_forward(module, x):
@@ -89,8 +140,15 @@ def encoder_forward(module, x):
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
         raise RuntimeError("x must be a tensor on an MI355X (HIP) device: eraft_amd has no CPU fallback")
     instance = module.norm_fn == "instance"
-    x = F.relu(module.norm1(module.conv1(x.detach()))).contiguous()
+    x, x_norm = x.detach().contiguous(), None
+    if USE_KERNEL["stem"] and x.shape[1] <= STEM_MAX_CIN:
+        packed, bias = _front_pack(module.conv1, _lib.enc_stem_pack_weights)
+        y = _lib.enc_stem_forward(x, packed, bias, module.conv1.out_channels, stats=instance)
+        x, st = y if instance else (y, None)
+        x_norm = _norm_of(x, st, module.norm1, instance)
+    else:
+        x = F.relu(module.norm1(module.conv1(x))).contiguous()
     for name in ("layer1", "layer2", "layer3"):
         for block in getattr(module, name):
-            x = _block(name, block, x, instance)
-    return module.conv2(x)
+            x, x_norm = _block(name, block, x, x_norm, instance), None
+    return _pw(module.conv2, x) if USE_KERNEL["head"] else module.conv2(x)

@@ -83,35 +83,48 @@ class BasicEncoder(nn.Module):
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
 
-    # ERAFT_AMD_FUSE_ENCODER=1: at inference on the MI355X the residual stages' 3x3 convolutions
-    # are corr_enc_conv_forward launches with the norms applied on load (encoder.py) instead of
-    # MIOpen convolutions and torch norm / ReLU / add kernels.  Default off (DESIGN §16 has the
-    # measurements); training always runs the torch code.
+    # ERAFT_AMD_FUSE_ENCODER=1: at inference on the MI355X the whole encoder runs on the project's
+    # kernels (encoder.py): the 7x7 stem, the residual stages' 3x3 convolutions, the strided blocks'
+    # 1x1 projections and the 1x1 head on the bf16x6 MFMA, every norm applied on load or in the
+    # block's join, instead of MIOpen / rocBLAS convolutions and torch norm / ReLU / add kernels.
+    # Default off (DESIGN §16 and §18 have the measurements); training always runs the torch code.
     fused = os.environ.get("ERAFT_AMD_FUSE_ENCODER", "0") == "1"
 
     def _fusable(self, x):
         """encoder.encoder_forward is built for an fp32 GPU tensor, instance norm or eval-mode
-        batch norm, the reference's channel counts, and has no backward."""
+        batch norm, the reference's shapes (stem 7x7 / 2 with padding 3 to 64 channels, 3x3 stages
+        of 64, 96, 128 channels, 1x1 projections and head, every convolution with a bias), and has
+        no backward."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
             return False
         if not (self.norm_fn == "instance" or (self.norm_fn == "batch" and not self.training)):
             return False
         if self.training and self.dropout is not None:
             return False
+
+        def conv_is(c, shape, stride, padding):
+            return (tuple(c.weight.shape) == shape and c.stride == (stride, stride) and c.padding == (padding, padding)
+                    and c.dilation == (1, 1) and c.groups == 1 and c.bias is not None)
+
+        def norm_ok(n):
+            if self.norm_fn == "instance":
+                return isinstance(n, nn.InstanceNorm2d) and not n.affine and not n.track_running_stats
+            return isinstance(n, nn.BatchNorm2d) and n.running_mean is not None and n.running_var is not None
+
+        if not (conv_is(self.conv1, (64, x.shape[1], 7, 7), 2, 3) and norm_ok(self.norm1)
+                and conv_is(self.conv2, (self.conv2.out_channels, 128, 1, 1), 1, 0)):
+            return False
         cin = 64
         for layer, cout, stride in ((self.layer1, 64, 1), (self.layer2, 96, 2), (self.layer3, 128, 2)):
             for k, blk in enumerate(layer):
                 s = stride if k == 0 else 1
-                if (tuple(blk.conv1.weight.shape) != (cout, cin, 3, 3) or tuple(blk.conv2.weight.shape) != (cout, cout, 3, 3)
-                        or blk.conv1.stride != (s, s) or blk.conv2.stride != (1, 1) or blk.conv1.bias is None
-                        or blk.conv2.bias is None or (blk.downsample is None) != (s == 1)):
+                if not (conv_is(blk.conv1, (cout, cin, 3, 3), s, 1) and conv_is(blk.conv2, (cout, cout, 3, 3), 1, 1)
+                        and norm_ok(blk.norm1) and norm_ok(blk.norm2) and (blk.downsample is None) == (s == 1)):
                     return False
-                for n in (blk.norm1, blk.norm2):
-                    if self.norm_fn == "instance":
-                        if not isinstance(n, nn.InstanceNorm2d) or n.affine or n.track_running_stats:
-                            return False
-                    elif not isinstance(n, nn.BatchNorm2d) or n.running_mean is None or n.running_var is None:
-                        return False
+                if s != 1 and not (len(blk.downsample) == 2 and isinstance(blk.downsample[0], nn.Conv2d)
+                                   and conv_is(blk.downsample[0], (cout, cin, 1, 1), s, 0)
+                                   and norm_ok(blk.downsample[1])):
+                    return False
                 cin = cout
         ts = list(self.parameters()) + list(self.buffers())
         if any(t.device != x.device or (t.is_floating_point() and t.dtype != torch.float32) for t in ts):

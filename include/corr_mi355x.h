@@ -595,6 +595,65 @@ int corr_enc_join(const float *y, const float *scale, const float *shift, int no
                   const float *skip, int B, int C, int H, int W, float *out, void *stream);
 
 /*
+ * The encoders around their residual stages (model/extractor.py:137-189: BasicEncoder's 7x7 stem,
+ * the strided blocks' 1x1 projections, the 1x1 head), inference only.  With them
+ *   y0 = stem(x);  layer1[0] reads relu(norm1(y0)) by norm on load and joins it as its skip;
+ *   a strided block's skip is norm3(pw(x)) [stride 2], applied by its join;  out = pw(layer3) [stride 1]
+ * so that no normalised map is stored.
+ *
+ * corr_enc_stem_forward: the 7x7 convolution at stride 2 with zero padding 3, bias, no ReLU:
+ *   out[b][o][y][x] = bias[o] + sum_c sum_ky sum_kx w[o][c][ky][kx] * in[b][c][2 y + ky - 3][2 x + kx - 3]
+ * in is [B][cin][H][W] (exactly cin planes are read), out [B][cout][Ho][Wo] with Ho = (H - 1) / 2
+ * + 1, Wo = (W - 1) / 2 + 1; odd sizes and sizes below 7 are allowed.  w is a contiguous Conv2d
+ * weight [cout][cin][7][7], split once per weight version by corr_enc_stem_pack_weights into a
+ * corr_enc_stem_weights_bytes(cout, cin) buffer (16-B aligned, opaque; 0 for unsupported sizes).
+ * K order: tap-major, tap = 7 ky + kx ascending, the channels of a tap ascending and padded with
+ * zeros to 16; a K step of 32 is two taps, 25 steps.
+ *
+ * corr_enc_pw_forward: the 1x1 convolution at stride s = 1 or 2, no padding, bias, no ReLU:
+ *   out[b][o][y][x] = bias[o] + sum_c w[o][c] * in[b][c][s y][s x]
+ * with Ho = (H - 1) / s + 1, Wo = (W - 1) / s + 1.  At stride 2 only the even rows and columns of
+ * in are read.  w is a contiguous [cout][cin] (a [cout][cin][1][1] Conv2d weight), split by
+ * corr_enc_pw_pack_weights into a corr_enc_pw_weights_bytes(cout, cin) buffer (16-B aligned,
+ * opaque; 0 for unsupported sizes).  K order: ascending 32-channel steps.
+ *
+ * Both: bias is [cout] or NULL; the packs hold the rows padded with zeros to a multiple of 64,
+ * padding rows are never stored.  Arithmetic: corr_conv_forward's (the bf16 MFMA with the exact
+ * three-piece split, six products per fp32 product in its order, fp32 accumulation in the K order
+ * above, then + bias; each fp32 op rounded once; deterministic; non-finite inputs are NOT
+ * parity-checked).  stats (may be NULL) is corr_enc_conv_forward's, layout and meaning:
+ * [B][cout][ceil(Ho/4) * ceil(Wo/16)][2] of (sum, M2 about the tile's own mean), at least
+ * corr_enc_stats_bytes(B, cout, Ho, Wo) bytes, for corr_enc_norm_finalize.  out's byte range must
+ * not overlap in's.
+ *
+ * corr_enc_join_affine: corr_enc_join with an affine (and optionally a ReLU) on the skip,
+ *   out = max(s(skip) + max(y * scale[k] + shift[k], 0), 0),   s(v) = v * skip_scale[k'] + skip_shift[k'],
+ * s(v) = max(., 0) of that when skip_relu = 1, s(v) = v (then the ReLU, if asked for) when
+ * skip_scale and skip_shift are both NULL.  k = b C + c (norm_per_batch = 1) or c (0), k' likewise
+ * by skip_per_batch.  Each fp32 op is rounded once.  out may be y (or skip) itself.
+ *
+ * Sizes: stem 1 <= cin <= 16 (a larger cin: CORR_EUNSUPPORTED), pointwise cin a multiple of 32 in
+ * 32 .. 1024, both 1 <= cout <= 1024, pointwise stride 1 or 2; otherwise CORR_EUNSUPPORTED.
+ * CORR_EINVAL: a NULL in, packed, out (pack: w, packed; join: y, scale, shift, skip, out); stem
+ * cin < 1; stats with stats_bytes too small; packed not 16-byte aligned; B, C, H or W < 1 or
+ * B*H*W >= 2^31 (join: B*C >= 2^31); out overlapping in; exactly one of skip_scale / skip_shift
+ * NULL; norm_per_batch, skip_per_batch or skip_relu not 0 or 1.  Every refusal comes before any
+ * HIP call.  No workspace, no allocation, no synchronisation; everything goes on `stream` and can
+ * be captured into a graph.
+ */
+size_t corr_enc_stem_weights_bytes(int cout, int cin);
+int corr_enc_stem_pack_weights(const float *w, int cout, int cin, void *packed, void *stream);
+int corr_enc_stem_forward(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
+                          int cout, float *out, void *stats, size_t stats_bytes, void *stream);
+size_t corr_enc_pw_weights_bytes(int cout, int cin);
+int corr_enc_pw_pack_weights(const float *w, int cout, int cin, void *packed, void *stream);
+int corr_enc_pw_forward(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
+                        const float *bias, int cout, float *out, void *stats, size_t stats_bytes, void *stream);
+int corr_enc_join_affine(const float *y, const float *scale, const float *shift, int norm_per_batch,
+                         const float *skip, const float *skip_scale, const float *skip_shift, int skip_per_batch,
+                         int skip_relu, int B, int C, int H, int W, float *out, void *stream);
+
+/*
  * The update block's mask head fused with the convex upsampling (model/update.py:99-107: the
  * 256 -> 576 1x1 convolution mask[2] and its 0.25; model/eraft.py:75-86 upsample_flow), inference
  * only: one launch from the hidden activations relu(mask[0](net)) and the 1/8-resolution flow to

@@ -1,16 +1,24 @@
-"""The encoders' residual stages on corr_enc_conv_forward vs the torch / MIOpen ops they replace.
+"""The encoders' pieces on the project's kernels vs the torch / MIOpen / rocBLAS ops they replace.
 Every variant is captured as one HIP graph and replayed; the variants of a measurement are
 alternated in ONE process on the same inputs, so box-to-box spread drops out.
-    python tools/bench_encoder.py [--sizes dsec,b8,hires1920] [--trials 5] [--json profiles/encoder_bench.json]
+    python tools/bench_encoder.py [--sizes dsec,b8,hires1920] [--kinds layer1.first,stem,...] [--trials 5]
+                                  [--json profiles/encoder_bench.json]
 Per size (the encoder's input; fnet sees both voxel grids as one batch, cnet one) and per encoder
 (fnet: instance norm, cnet: eval-mode batch norm):
   (a) each kind of convolution against the torch ops it replaces.  "first": a block's conv1 (at
       its stride), torch conv + norm + ReLU against the kernel with statistics + finalize (instance)
       or the kernel alone (batch; the norm and the ReLU are its consumer's).  "second": a block's
       conv2, torch conv + norm + ReLU + add + ReLU against the kernel with norm on load (and
-      statistics + finalize) + join;
-  (b) one whole encoder call with the switch off, with every convolution on the kernel ("all"), and
-      with the committed table encoder.USE_KERNEL ("fused").
+      statistics + finalize) + join.  "stem": torch conv 7x7 + norm + ReLU, then corr_enc_join of a
+      fixed y with that map as its skip, against the stem kernel (+ finalize) and
+      corr_enc_join_affine of the same y with the raw map; "layerN.proj": torch downsample(x) (1x1
+      conv + norm) and corr_enc_join against the pointwise kernel (+ finalize) and
+      corr_enc_join_affine; "head": torch conv2 against the pointwise kernel.  Both sides of a stem
+      or projection row carry one join, so their difference holds the extra skip arithmetic;
+  (b) one whole encoder call with the switch off, with the stem, the projections and the head on
+      torch and the 3x3 convolutions on the committed table ("stages": the switch before these
+      pieces had kernels), with every piece on the kernel ("all"), and with the committed table
+      encoder.USE_KERNEL ("fused").
 Median / min / max ms per call over the trial windows; for (a) each path's norm-relative error
 against the same formula in fp64 on the GPU, for (b) the kernel path's norm-relative difference
 from the torch path (the parity against the reference is tests/test_encoder.py's).  Prints one JSON
@@ -35,6 +43,7 @@ SIZES = {"dsec": (1, 15, 480, 640), "b8": (8, 15, 288, 384), "hires1920": (1, 15
 KINDS = {"layer1.first": ("layer1", 0, True), "layer1.second": ("layer1", 0, False),
          "layer2.s2": ("layer2", 0, True), "layer2.first": ("layer2", 1, True), "layer2.second": ("layer2", 0, False),
          "layer3.s2": ("layer3", 0, True), "layer3.first": ("layer3", 1, True), "layer3.second": ("layer3", 0, False)}
+FRONT = ("stem", "layer2.proj", "layer3.proj", "head")
 
 
 def norm_rel(a, b):
@@ -95,7 +104,44 @@ def alternate(graphs, trials, budget=0.15):
     return res
 
 
-def bench_encoder(m, x, which, trials, stream):
+def front_fns(m, kind, x, maps, instance):
+    """(torch_fn, kernel_fn, check, ref, src) of one of the FRONT rows."""
+    if kind == "head":
+        with torch.no_grad():
+            src = m.layer3(maps["layer3"])
+            ref = F.conv2d(src.double(), m.conv2.weight.double(), m.conv2.bias.double())
+        return (lambda: m.conv2(src)), (lambda: encoder._pw(m.conv2, src)), (lambda o: o), ref, src
+    if kind == "stem":
+        src, conv, norm, relu = x, m.conv1, m.norm1, True
+    else:
+        block = getattr(m, kind.split(".")[0])[0]
+        src, conv, norm, relu = maps[kind.split(".")[0]], block.downsample[0], block.downsample[1], False
+    with torch.no_grad():
+        raw = conv(src)
+        y = torch.randn_like(raw)
+        sc = 1.0 + 0.1 * torch.randn(raw.shape[:2] if instance else raw.shape[1:2], device=x.device)
+        sh = 0.1 * torch.randn_like(sc)
+        skip = norm64(norm, F.conv2d(src.double(), conv.weight.double(), conv.bias.double(), stride=conv.stride,
+                                     padding=conv.padding))
+        view = (raw.shape[0], raw.shape[1], 1, 1) if instance else (1, raw.shape[1], 1, 1)
+        ref = F.relu((F.relu(skip) if relu else skip) + F.relu(y.double() * sc.double().view(view) + sh.double().view(view)))
+
+    def torch_fn():
+        s = norm(conv(src))
+        return _lib.enc_join(y, sc, sh, F.relu(s) if relu else s)
+
+    def kernel_fn():
+        if kind == "stem":
+            packed, bias = encoder._front_pack(conv, _lib.enc_stem_pack_weights)
+            p = _lib.enc_stem_forward(src, packed, bias, conv.out_channels, stats=instance)
+        else:
+            p = encoder._pw(conv, src, stats=instance)
+        p, st = p if instance else (p, None)
+        return _lib.enc_join_affine(y, sc, sh, p, *encoder._norm_of(p, st, norm, instance), skip_relu=relu)
+    return torch_fn, kernel_fn, (lambda o: o), ref, src
+
+
+def bench_encoder(m, x, which, trials, stream, kinds):
     """(a) and (b) for one encoder `m` on the input x."""
     instance = m.norm_fn == "instance"
     res = {"norm": m.norm_fn, "B": x.shape[0], "convs": {}}
@@ -103,9 +149,13 @@ def bench_encoder(m, x, which, trials, stream):
         maps = {"layer1": F.relu(m.norm1(m.conv1(x)))}
         maps["layer2"] = m.layer1(maps["layer1"])
         maps["layer3"] = m.layer2(maps["layer2"])
-    for kind, (layer, blk, first) in KINDS.items():
-        block = getattr(m, layer)[blk]
-        if first:
+    for kind in kinds:
+        layer, blk, first = KINDS.get(kind, (None, 0, False))
+        block = getattr(m, layer)[blk] if layer else None
+        if kind in FRONT:
+            torch_fn, kernel_fn, check, ref, src = front_fns(m, kind, x, maps, instance)
+            conv = {"stem": m.conv1, "head": m.conv2}.get(kind) or getattr(m, kind.split(".")[0])[0].downsample[0]
+        elif first:
             with torch.no_grad():
                 src = maps[layer] if blk == 0 else getattr(m, layer)[0](maps[layer])
                 conv, norm = block.conv1, block.norm1
@@ -148,7 +198,9 @@ def bench_encoder(m, x, which, trials, stream):
 
     table = {k: v for k, v in encoder.USE_KERNEL.items() if k != "on"}
     graphs, outs, keep = {}, {}, []
-    for vname, on, tab in (("torch", False, table), ("all", True, dict.fromkeys(table, True)), ("fused", True, table)):
+    stages = dict(table, **dict.fromkeys(FRONT, False))
+    for vname, on, tab in (("torch", False, table), ("stages", True, stages), ("all", True, dict.fromkeys(table, True)),
+                           ("fused", True, table)):
         BasicEncoder.fused = on
         encoder.USE_KERNEL.update(tab)
         graphs[vname], outs[vname], k = capture(lambda: m(x), stream)
@@ -156,7 +208,7 @@ def bench_encoder(m, x, which, trials, stream):
     BasicEncoder.fused = False
     encoder.USE_KERNEL.update(table)
     r = alternate(graphs, trials)
-    for vname in ("all", "fused"):
+    for vname in ("stages", "all", "fused"):
         r[vname]["vs_torch_rel"] = norm_rel(outs[vname], outs["torch"])
         r[f"{vname}_over_torch"] = round(r[vname]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
     r["use_kernel"] = table
@@ -166,7 +218,7 @@ def bench_encoder(m, x, which, trials, stream):
     return res
 
 
-def bench_size(name, trials, dev):
+def bench_size(name, trials, dev, kinds):
     pairs, C, H, W = SIZES[name]
     torch.manual_seed(1234)
     stream = torch.cuda.Stream()
@@ -180,7 +232,7 @@ def bench_size(name, trials, dev):
                         mod.running_mean.normal_(0.0, 0.1)
                         mod.running_var.uniform_(0.5, 1.5)
         x = torch.randn(B, C, H, W, device=dev) * (torch.rand(B, C, H, W, device=dev) < 0.15)
-        res[which] = bench_encoder(m, x, which, trials, stream)
+        res[which] = bench_encoder(m, x, which, trials, stream, kinds)
         del m, x
         torch.cuda.empty_cache()
     return res
@@ -189,6 +241,7 @@ def bench_size(name, trials, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="dsec,b8,hires1920")
+    ap.add_argument("--kinds", default=",".join(list(KINDS) + list(FRONT)), help="the rows of (a) to measure")
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -196,12 +249,15 @@ def main():
         sys.exit("bench_encoder needs an MI355X (no CPU fallback)")
     if a.trials < 5:
         sys.exit("--trials must be >= 5 (the median of at least 5 windows is reported)")
+    kinds = [k for k in a.kinds.split(",") if k]
+    if any(k not in KINDS and k not in FRONT for k in kinds):
+        sys.exit(f"--kinds must be among {list(KINDS) + list(FRONT)}")
     dev = torch.device("cuda", 0)
     encoder.USE_KERNEL["on"] = True  # the key the single-convolution measurements run under
     doc = {"device": torch.cuda.get_device_name(0),
            "call": "one HIP graph per variant, variants alternated; convs: kernel launches vs the torch ops they "
                    "replace; whole: BasicEncoder.forward",
-           "sizes": {n: bench_size(n, a.trials, dev) for n in a.sizes.split(",")}}
+           "sizes": {n: bench_size(n, a.trials, dev, kinds) for n in a.sizes.split(",")}}
     del encoder.USE_KERNEL["on"]
     text = json.dumps(doc, indent=1)
     print(text)
