@@ -889,6 +889,125 @@ int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hid
                       fn);
 }
 
+size_t corr_flow_enc_weights_bytes(int cout) {
+    if (!flow_enc_supported(cout)) return 0;
+    return flow_enc_weights_bytes(cout);
+}
+
+static int check_flow_enc_channels(const char *fn, int cout) {
+    if (!flow_enc_supported(cout))
+        return fail(CORR_EUNSUPPORTED, "%s: built for 1 <= cout <= 1024 (got cout = %d)", fn, cout);
+    return CORR_OK;
+}
+
+int corr_flow_enc_pack_weights(const float *w, int cout, void *packed, void *stream) {
+    static const char *fn = "corr_flow_enc_pack_weights";
+    g_err[0] = 0;
+    int rc;
+    if ((rc = check_flow_enc_channels(fn, cout))) return rc;
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_flow_enc_pack(w, cout, packed, (hipStream_t)stream), fn);
+}
+
+int corr_flow_enc_forward(const float *flow, int B, int H, int W, const void *packed, const float *bias, int cout,
+                          int relu, float *out, int out_channels, int out_offset, float *flow_copy,
+                          int copy_channels, int copy_offset, void *stream) {
+    static const char *fn = "corr_flow_enc_forward";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    if ((rc = check_flow_enc_channels(fn, cout))) return rc;
+    if (relu != 0 && relu != 1) return fail(CORR_EINVAL, "%s: relu must be 0 or 1 (got %d)", fn, relu);
+    if (out_offset < 0 || (long long)out_offset + cout > out_channels)
+        return fail(CORR_EINVAL, "%s: channels out_offset .. out_offset + cout - 1 must lie in [0, out_channels) "
+                                 "(got out_offset = %d, cout = %d, out_channels = %d)",
+                    fn, out_offset, cout, out_channels);
+    if ((rc = check_ptr(fn, flow, "flow")) || (rc = check_ptr(fn, packed, "packed")) ||
+        (rc = check_ptr(fn, out, "out")))
+        return rc;
+    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    const long double px = (long double)B * H * W * sizeof(float), ob = px * out_channels;
+    if (ob > (long double)(SIZE_MAX / 2)) return fail(CORR_EINVAL, "%s: B*out_channels*H*W too large", fn);
+    if (ranges_overlap(out, ob, flow, px * 2)) return fail(CORR_EINVAL, "%s: out must not overlap flow", fn);
+    if (flow_copy) {
+        if ((rc = check_ptr(fn, flow_copy, "flow_copy"))) return rc;
+        if (copy_offset < 0 || (long long)copy_offset + 2 > copy_channels)
+            return fail(CORR_EINVAL, "%s: channels copy_offset, copy_offset + 1 must lie in [0, copy_channels) "
+                                     "(got copy_offset = %d, copy_channels = %d)",
+                        fn, copy_offset, copy_channels);
+        const long double cb = px * copy_channels;
+        if (cb > (long double)(SIZE_MAX / 2)) return fail(CORR_EINVAL, "%s: B*copy_channels*H*W too large", fn);
+        if (ranges_overlap(flow_copy, cb, flow, px * 2))
+            return fail(CORR_EINVAL, "%s: flow_copy must not overlap flow", fn);
+        // out and flow_copy may be one tensor written through disjoint channel windows, nothing else
+        if (ranges_overlap(flow_copy, cb, out, ob)) {
+            const bool disjoint = copy_offset + 2 <= out_offset || (long long)out_offset + cout <= copy_offset;
+            if (flow_copy != out || copy_channels != out_channels || !disjoint)
+                return fail(CORR_EINVAL, "%s: out and flow_copy overlap (one tensor with disjoint channel windows "
+                                         "is the only overlap accepted)",
+                            fn);
+        }
+    }
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_flow_enc(flow, B, H, W, packed, bias, cout, relu, out, out_channels, out_offset,
+                                      flow_copy, copy_channels, copy_offset, (hipStream_t)stream),
+                      fn);
+}
+
+size_t corr_flow_head_weights_bytes(void) { return flow_head_weights_bytes(); }
+
+int corr_flow_head_pack_weights(const float *w, void *packed, void *stream) {
+    static const char *fn = "corr_flow_head_pack_weights";
+    g_err[0] = 0;
+    int rc;
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_flow_head_pack(w, packed, (hipStream_t)stream), fn);
+}
+
+int corr_flow_head_forward(const float *hidden, int hidden_channels, int hidden_offset, int B, int H, int W,
+                           const void *packed, const float *bias, const float *coords_in, const float *coords0,
+                           float *delta, float *coords_out, float *flow_out, void *stream) {
+    static const char *fn = "corr_flow_head_forward";
+    g_err[0] = 0;
+    int rc = check_dims(fn, B, 1, H, W, 1);
+    if (rc) return rc;
+    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    if (hidden_offset < 0 || (long long)hidden_offset + 256 > hidden_channels)
+        return fail(CORR_EINVAL, "%s: channels hidden_offset .. hidden_offset + 255 must lie in [0, hidden_channels) "
+                                 "(got hidden_offset = %d, hidden_channels = %d)",
+                    fn, hidden_offset, hidden_channels);
+    if ((rc = check_ptr(fn, hidden, "hidden")) || (rc = check_ptr(fn, packed, "packed")) ||
+        (rc = check_ptr(fn, bias, "bias")) || (rc = check_ptr(fn, delta, "delta")))
+        return rc;
+    if (coords0 && !coords_in) return fail(CORR_EINVAL, "%s: coords0 needs coords_in", fn);
+    if (coords_in && ((rc = check_ptr(fn, coords_in, "coords_in")) || (rc = check_ptr(fn, coords_out, "coords_out"))))
+        return rc;
+    if (coords0 && ((rc = check_ptr(fn, coords0, "coords0")) || (rc = check_ptr(fn, flow_out, "flow_out")))) return rc;
+    const long double px = (long double)B * H * W * sizeof(float), hb = px * hidden_channels, cb = px * 2;
+    if (hb > (long double)(SIZE_MAX / 2)) return fail(CORR_EINVAL, "%s: B*hidden_channels*H*W too large", fn);
+    // the outputs that this call writes, against every input and each other
+    const void *outs[3] = {delta, coords_in ? coords_out : nullptr, coords0 ? flow_out : nullptr};
+    static const char *names[3] = {"delta", "coords_out", "flow_out"};
+    for (int k = 0; k < 3; ++k) {
+        if (!outs[k]) continue;
+        if (ranges_overlap(outs[k], cb, hidden, hb) || (coords_in && ranges_overlap(outs[k], cb, coords_in, cb)) ||
+            (coords0 && ranges_overlap(outs[k], cb, coords0, cb)))
+            return fail(CORR_EINVAL, "%s: %s must not overlap hidden, coords_in or coords0 (no in-place update)", fn,
+                        names[k]);
+        for (int j = 0; j < k; ++j)
+            if (outs[j] && ranges_overlap(outs[k], cb, outs[j], cb))
+                return fail(CORR_EINVAL, "%s: %s must not overlap %s", fn, names[k], names[j]);
+    }
+    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    return hip_status(launch_flow_head(hidden, hidden_channels, hidden_offset, B, H, W, packed, bias, coords_in,
+                                       coords0, delta, coords_in ? coords_out : nullptr, coords0 ? flow_out : nullptr,
+                                       (hipStream_t)stream),
+                      fn);
+}
+
 size_t corr_convex_upsample_bwd_workspace(int N, int h, int w) {
     if (N < 1 || h < 1 || w < 1) return 0;
     return convex_upsample_bwd_workspace(N, h, w);

@@ -250,6 +250,19 @@ hipError_t launch_mask_upsample_pack(const float *w, void *packed, hipStream_t s
 hipError_t launch_mask_upsample(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
                                 const void *packed, const float *bias, float mask_scale, int B, int H, int W,
                                 float *out, hipStream_t s);
+// The update block's tail (corr_flow.hip): the 7x7 convolution of the flow with the flow's
+// pass-through, and the flow head's 3x3 to 2 channels with the coordinate update.
+bool flow_enc_supported(int cout);
+size_t flow_enc_weights_bytes(int cout);
+hipError_t launch_flow_enc_pack(const float *w, int cout, void *packed, hipStream_t s);
+hipError_t launch_flow_enc(const float *flow, int B, int H, int W, const void *packed, const float *bias, int cout,
+                           int relu, float *out, int out_channels, int out_offset, float *flow_copy,
+                           int copy_channels, int copy_offset, hipStream_t s);
+size_t flow_head_weights_bytes();
+hipError_t launch_flow_head_pack(const float *w, void *packed, hipStream_t s);
+hipError_t launch_flow_head(const float *hidden, int hidden_channels, int hidden_offset, int B, int H, int W,
+                            const void *packed, const float *bias, const float *coords_in, const float *coords0,
+                            float *delta, float *coords_out, float *flow_out, hipStream_t s);
 size_t build_bwd_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bwd(const float *grad_c, const float *f1, int NQ, const float *f2, int B,
                             int D, int H, int W, float *df1, float *df2, float *ws, hipStream_t s);

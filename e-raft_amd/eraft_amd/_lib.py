@@ -38,7 +38,9 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_enc_norm_finalize", "corr_enc_join", "corr_mask_upsample_weights_bytes",
            "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_stem_weights_bytes",
            "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_weights_bytes",
-           "corr_enc_pw_pack_weights", "corr_enc_pw_forward", "corr_enc_join_affine")
+           "corr_enc_pw_pack_weights", "corr_enc_pw_forward", "corr_enc_join_affine",
+           "corr_flow_enc_weights_bytes", "corr_flow_enc_pack_weights", "corr_flow_enc_forward",
+           "corr_flow_head_weights_bytes", "corr_flow_head_pack_weights", "corr_flow_head_forward")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -170,7 +172,14 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_mask_upsample_weights_bytes.argtypes, lib.corr_mask_upsample_weights_bytes.restype = [], sz
     lib.corr_mask_upsample_pack_weights.argtypes = [vp, vp, vp]
     lib.corr_mask_upsample_forward.argtypes = [vp, i, i, vp, vp, vp, ctypes.c_float, i, i, i, vp, vp]
-    for f in ("corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
+    lib.corr_flow_enc_weights_bytes.argtypes, lib.corr_flow_enc_weights_bytes.restype = [i], sz
+    lib.corr_flow_enc_pack_weights.argtypes = [vp, i, vp, vp]
+    lib.corr_flow_enc_forward.argtypes = [vp, i, i, i, vp, vp, i, i, vp, i, i, vp, i, i, vp]
+    lib.corr_flow_head_weights_bytes.argtypes, lib.corr_flow_head_weights_bytes.restype = [], sz
+    lib.corr_flow_head_pack_weights.argtypes = [vp, vp, vp]
+    lib.corr_flow_head_forward.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    for f in ("corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
+              "corr_flow_head_forward", "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
               "corr_enc_join_affine", "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
@@ -814,6 +823,140 @@ def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=
         _check(lib.corr_mask_upsample_forward(hp, hc, hidden_offset, fp, pk, bp, float(scale), B, H, W, op,
                                               _stream(hidden)))
     return out
+
+
+def flow_enc_pack_weights(w):
+    """corr_flow_enc_pack_weights: a Conv2d weight [cout, 2, 7, 7] -> the packed split (an opaque
+    buffer)."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("w must be a torch.Tensor")
+    if w.dim() != 4 or tuple(w.shape[1:]) != (2, 7, 7):
+        raise ValueError(f"w must be [cout, 2, 7, 7] (got {tuple(w.shape)})")
+    w = w.detach().float().contiguous()
+    cout = w.shape[0]
+    lib = load()
+    n = lib.corr_flow_enc_weights_bytes(cout)
+    if n == 0:
+        raise CorrError(CORR_EUNSUPPORTED, f"corr_flow_enc_weights_bytes: unsupported cout = {cout}")
+    wp = _dev(w, "w")
+    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib.corr_flow_enc_pack_weights(wp, cout, packed.data_ptr(), _stream(w)))
+    return packed
+
+
+def flow_enc_forward(flow, packed, bias, cout, relu, out=None, out_offset=0, flow_copy=None, copy_offset=0):
+    """corr_flow_enc_forward: the 7x7 convolution (+ bias, + ReLU) of flow [B, 2, H, W] with the
+    pack of flow_enc_pack_weights, written into channels out_offset .. + cout - 1 of `out`
+    [B, out_channels, H, W] (allocated as [B, cout, H, W] when None).  With `flow_copy`
+    [B, copy_channels, H, W] the flow is also copied into its channels copy_offset, + 1.
+    Returns `out`."""
+    fp = _dev(flow, "flow")
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError(f"flow must be [B, 2, H, W] (got {tuple(flow.shape)})")
+    B, _, H, W = flow.shape
+    lib = load()
+    need = lib.corr_flow_enc_weights_bytes(cout)
+    if need == 0:
+        raise CorrError(CORR_EUNSUPPORTED, f"corr_flow_enc_forward: unsupported cout = {cout}")
+    pk = _dev(packed, "packed")
+    if packed.numel() * 4 < need or packed.device != flow.device:
+        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
+                         f"{need} on {flow.device}")
+    biasp = None
+    if bias is not None:
+        biasp = _dev(bias, "bias")
+        if bias.numel() != cout or bias.device != flow.device:
+            raise ValueError(f"bias must hold cout = {cout} values on {flow.device} (got {tuple(bias.shape)})")
+    if out is None:
+        if out_offset != 0:
+            raise ValueError("out_offset needs an out tensor")
+        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=flow.device)
+    op = _dev(out, "out")
+    if (out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (H, W) or out.device != flow.device
+            or out_offset < 0 or out_offset + cout > out.shape[1]):
+        raise ValueError(f"out {tuple(out.shape)} does not hold channels {out_offset} .. {out_offset + cout - 1} "
+                         f"of a [{B}, *, {H}, {W}] map on {flow.device}")
+    cp, cc = None, 0
+    if flow_copy is not None:
+        cp = _dev(flow_copy, "flow_copy")
+        if (flow_copy.dim() != 4 or flow_copy.shape[0] != B or tuple(flow_copy.shape[2:]) != (H, W)
+                or flow_copy.device != flow.device or copy_offset < 0 or copy_offset + 2 > flow_copy.shape[1]):
+            raise ValueError(f"flow_copy {tuple(flow_copy.shape)} does not hold channels {copy_offset}, "
+                             f"{copy_offset + 1} of a [{B}, *, {H}, {W}] map on {flow.device}")
+        cc = flow_copy.shape[1]
+    elif copy_offset != 0:
+        raise ValueError("copy_offset needs a flow_copy tensor")
+    with torch.cuda.device(flow.device):
+        _check(lib.corr_flow_enc_forward(fp, B, H, W, pk, biasp, cout, int(bool(relu)), op, out.shape[1], out_offset,
+                                         cp, cc, copy_offset, _stream(flow)))
+    return out
+
+
+def flow_head_pack_weights(w):
+    """corr_flow_head_pack_weights: the flow head's second Conv2d weight [2, 256, 3, 3] -> the packed
+    split (an opaque buffer)."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("w must be a torch.Tensor")
+    if tuple(w.shape) != (2, 256, 3, 3):
+        raise ValueError(f"w must be [2, 256, 3, 3] (got {tuple(w.shape)})")
+    w = w.detach().float().contiguous()
+    wp = _dev(w, "w")
+    lib = load()
+    packed = torch.empty((lib.corr_flow_head_weights_bytes() + 3) // 4, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib.corr_flow_head_pack_weights(wp, packed.data_ptr(), _stream(w)))
+    return packed
+
+
+def flow_head_forward(hidden, hidden_offset, packed, bias, coords_in=None, coords0=None, delta=None,
+                      coords_out=None, flow_out=None):
+    """corr_flow_head_forward: delta = the 3x3 convolution (+ bias) of hidden[:, hidden_offset:
+    hidden_offset + 256] (read in place) with the pack of flow_head_pack_weights; with `coords_in`
+    also coords_out = coords_in + delta, and with `coords0` as well flow_out = coords_out - coords0.
+    All of these are [B, 2, H, W]; the outputs are allocated when None and must not alias an
+    input.  Returns (delta, coords_out, flow_out), None for what was not asked for."""
+    hp = _dev(hidden, "hidden")
+    if hidden.dim() != 4:
+        raise ValueError(f"hidden must be [B, C, H, W] (got {tuple(hidden.shape)})")
+    B, hc, H, W = hidden.shape
+    hidden_offset = int(hidden_offset)
+    if hidden_offset < 0 or hidden_offset + 256 > hc:
+        raise ValueError(f"hidden {tuple(hidden.shape)} does not hold channels {hidden_offset} .. "
+                         f"{hidden_offset + 255}")
+    lib = load()
+    need = lib.corr_flow_head_weights_bytes()
+    pk = _dev(packed, "packed")
+    if packed.numel() * 4 < need or packed.device != hidden.device:
+        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the flow head needs "
+                         f"{need} on {hidden.device}")
+    bp = _dev(bias, "bias")
+    if bias.numel() != 2 or bias.device != hidden.device:
+        raise ValueError(f"bias must hold 2 values on {hidden.device} (got {tuple(bias.shape)})")
+    if coords0 is not None and coords_in is None:
+        raise ValueError("coords0 needs coords_in")
+
+    def two(t, name, make):
+        if t is None:
+            if not make:
+                return None, None
+            t = torch.empty((B, 2, H, W), dtype=torch.float32, device=hidden.device)
+        p = _dev(t, name)
+        if tuple(t.shape) != (B, 2, H, W) or t.device != hidden.device:
+            raise ValueError(f"{name} must be [{B}, 2, {H}, {W}] on {hidden.device} (got {tuple(t.shape)} on "
+                             f"{t.device})")
+        return t, p
+
+    _, cip = two(coords_in, "coords_in", False)
+    _, c0p = two(coords0, "coords0", False)
+    delta, dp = two(delta, "delta", True)
+    coords_out, cop = two(coords_out, "coords_out", coords_in is not None)
+    flow_out, fop = two(flow_out, "flow_out", coords0 is not None)
+    # (an output whose input is missing is passed on as it is: the library leaves it untouched)
+    with torch.cuda.device(hidden.device):
+        _check(lib.corr_flow_head_forward(hp, hc, hidden_offset, B, H, W, pk, bp, cip, c0p, dp, cop, fop,
+                                          _stream(hidden)))
+    return delta, coords_out if coords_in is not None else None, flow_out if coords0 is not None else None
 
 
 def _enc_norm(scale, shift, B, C, device, name):

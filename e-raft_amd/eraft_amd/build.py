@@ -18,7 +18,8 @@ SO_PATH = os.path.join(OUT_DIR, SO_NAME)
 SOURCES = ["corr_build.hip", "corr_build_split.hip", "corr_build_bf16.hip", "corr_lookup.hip", "corr_lookup_conv.hip",
            "corr_lookup_bwd.hip", "corr_lookup_fold.hip", "corr_ondemand.hip", "corr_ondemand_bwd.hip", "corr_bwd.hip",
            "corr_bwd_split.hip", "corr_splat.hip", "corr_upsample.hip", "corr_voxel.hip", "corr_gru.hip",
-           "corr_conv.hip", "corr_enc_front.hip", "corr_mask_upsample.hip", "corr_api.cpp"]
+           "corr_conv.hip", "corr_enc_front.hip", "corr_mask_upsample.hip", "corr_flow.hip",
+           "corr_api.cpp"]
 # every header counts as a dependency of every translation unit (paths relative to csrc/)
 HEADERS = sorted(glob.glob("*.h", root_dir=SRC)) + [os.path.join("..", "..", "include", "corr_mi355x.h")]
 

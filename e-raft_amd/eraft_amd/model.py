@@ -225,8 +225,10 @@ class BasicUpdateBlock(nn.Module):
 
     # ERAFT_AMD_FUSE_UPDATE=1: at inference on the MI355X the block's 3x3 convolutions are
     # corr_conv_forward launches that write into shared buffers (update.py: no cat, bias and ReLU
-    # in the kernel) instead of MIOpen convolutions and torch glue.  Default off (DESIGN §15 has
-    # the measurements); training always runs the torch code.
+    # in the kernel) instead of MIOpen convolutions and torch glue; the flow's 7x7 convolution and
+    # the flow head's 3x3 to 2 channels, with the coordinate update, are corr_flow_enc_forward and
+    # corr_flow_head_forward launches.  Default off (DESIGN §15 and §19 have the measurements);
+    # training always runs the torch code.
     fused = os.environ.get("ERAFT_AMD_FUSE_UPDATE", "0") == "1"
 
     def __init__(self, corr_levels=4, corr_radius=4, hidden_dim=128):
@@ -251,23 +253,36 @@ class BasicUpdateBlock(nn.Module):
                   (self.mask[0], (256, 128, 3, 3)))
         if any(tuple(c.weight.shape) != s or c.bias is None for c, s in shapes):
             return False
+        # the flow's 7x7 and the flow head's 3x3 to 2 channels have kernels of their own (corr_flow.hip)
+        for c, s, pad in ((enc.convf1, (128, 2, 7, 7), 3), (self.flow_head.conv2, (2, 256, 3, 3), 1)):
+            if (tuple(c.weight.shape) != s or c.bias is None or c.padding != (pad, pad) or c.stride != (1, 1)
+                    or c.dilation != (1, 1) or c.groups != 1):
+                return False
         ps = list(self.parameters())
         if any(p.dtype != torch.float32 or p.device != net.device for p in ps):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in (*ts, *ps)))
 
-    def forward(self, net, inp, corr, flow, fused=False, defer_mask=False):
+    def forward(self, net, inp, corr, flow, fused=False, defer_mask=False, workspace=None, coords1=None,
+                coords0=None):
         """Returns (net, mask, delta_flow).  With `defer_mask`: (net, hidden, delta_flow), hidden =
         relu(mask[0](net)) [B, 256, H, W], and mask[2] with its 0.25 is left to the caller
-        (upsample.mask_upsample)."""
+        (upsample.mask_upsample).  With `coords1` the refinement loop's coordinate update is part
+        of the call: the result is (net, mask, delta_flow, coords1 + delta_flow, that - coords0),
+        the last None without `coords0`; on the fused path the flow head's kernel writes both.
+        `workspace` (update.UpdateWorkspace) keeps the fused path's buffers across iterations."""
         if self.fused and self._fusable(net, inp, corr, flow, fused):
             from .update import update_block
-            return update_block(self, net, inp, corr, flow, fused, defer_mask=defer_mask)
+            return update_block(self, net, inp, corr, flow, fused, defer_mask=defer_mask, workspace=workspace,
+                                coords1=coords1, coords0=coords0)
         motion = self.encoder(flow, corr, fused)
         net = self.gru(net, torch.cat([inp, motion], dim=1))
-        if defer_mask:
-            return net, self.mask[1](self.mask[0](net)), self.flow_head(net)
-        return net, 0.25 * self.mask(net), self.flow_head(net)
+        mask = self.mask[1](self.mask[0](net)) if defer_mask else 0.25 * self.mask(net)
+        delta = self.flow_head(net)
+        if coords1 is None:
+            return net, mask, delta
+        coords1 = coords1 + delta
+        return net, mask, delta, coords1, None if coords0 is None else coords1 - coords0
 
 
 class ImagePadder:
@@ -402,22 +417,35 @@ class ERAFT(nn.Module):
         # its autograd backward (corr._LookupConvFn), in training
         fuse = (self.fuse_lookup_conv and image1.is_cuda and self.corr_radius == 4
                 and hasattr(corr_fn, "lookup_conv"))
+        # with ERAFT_AMD_FUSE_UPDATE=1 at inference the update block keeps its buffers in a workspace
+        # made once per forward and its flow head's kernel also does the coordinate update: the loop
+        # then issues no coords1 + delta and no coords1 - coords0 (flow is the kernel's flow_out)
+        ub, ws, flow = self.update_block, None, None
         for _ in range(iters):
             coords1 = coords1.detach()
             if fuse:
-                enc = self.update_block.encoder
+                enc = ub.encoder
                 corr = corr_fn.lookup_conv(coords1, enc.convc1.weight, enc.convc1.bias)
             else:
                 corr = corr_fn(coords1)
+            if flow is None:
+                flow = coords1 - coords0
+            tail = ub.fused and ub._fusable(net, inp, corr, flow, fuse)
+            kw = {}
+            if tail:
+                if ws is None:
+                    from .update import UpdateWorkspace
+                    ws = UpdateWorkspace(inp.detach())
+                kw = {"workspace": ws, "coords1": coords1, "coords0": coords0}
             if self.fuse_mask_upsample and self._mask_fusable(net, inp, corr, coords1):
                 from .upsample import channel_window, mask_upsample
-                net, hidden, delta = self.update_block(net, inp, corr, coords1 - coords0, fuse, defer_mask=True)
-                coords1 = coords1 + delta
+                net, hidden, delta, *upd = ub(net, inp, corr, flow, fuse, defer_mask=True, **kw)
+                coords1, flow = upd if tail else (coords1 + delta, None)
                 hidden, off = channel_window(hidden)
-                up = mask_upsample(self.update_block.mask[2], hidden, off, coords1 - coords0)
+                up = mask_upsample(ub.mask[2], hidden, off, flow if tail else coords1 - coords0)
             else:
-                net, up_mask, delta = self.update_block(net, inp, corr, coords1 - coords0, fuse)
-                coords1 = coords1 + delta
-                up = self.upsample_flow(coords1 - coords0, up_mask)
+                net, up_mask, delta, *upd = ub(net, inp, corr, flow, fuse, **kw)
+                coords1, flow = upd if tail else (coords1 + delta, None)
+                up = self.upsample_flow(flow if tail else coords1 - coords0, up_mask)
             predictions.append(self.image_padder.unpad(up))
-        return coords1 - coords0, predictions
+        return (flow if flow is not None else coords1 - coords0), predictions

@@ -1,9 +1,11 @@
 """BasicUpdateBlock on the MI355X: the block's 3x3 convolutions (convc2, convf2, conv and the two
 heads' first convolutions) as corr_conv_forward launches (csrc/corr_conv.hip: bf16 MFMA with the
 exact three-piece split, bias and ReLU in the epilogue) that write straight into the buffer their
-consumer reads, so the motion encoder's two cats and the [inp, motion] cat go away.  Inference
-only: there is no backward, so model.BasicUpdateBlock takes this path only when autograd is not
-recording.
+consumer reads, so the motion encoder's two cats and the [inp, motion] cat go away; the 7x7
+convolution of the flow (convf1) as a corr_flow_enc_forward launch that also drops the flow into
+the GRU input, and the flow head's second convolution as a corr_flow_head_forward launch that also
+updates the coordinates (csrc/corr_flow.hip).  Inference only: there is no backward, so
+model.BasicUpdateBlock takes this path only when autograd is not recording.
 """
 from __future__ import annotations
 
@@ -14,32 +16,54 @@ import torch.nn.functional as F
 
 from . import _lib
 
-# Which convolutions take the HIP kernel under the switch (each is judged on its own
-# against the torch ops it replaces, at DSEC and at b8).  One that is False runs on MIOpen and is
-# copied into the shared buffer.
-USE_KERNEL = {"convc2": True, "convf2": True, "conv": True, "heads": True}
+# Which convolutions take the HIP kernel under the switch (each is judged on its
+# own against the torch ops it replaces, at DSEC and at b8).  One that is False runs on MIOpen and
+# is copied into the shared buffer.
+USE_KERNEL = {"convc2": True, "convf2": True, "conv": True, "heads": True, "convf1": True, "flow_head2": True}
 
-_CONV_PACKS = {}  # ids of the weights and biases -> (weakrefs to them, their (data_ptr, _version)s, pack, bias)
+# (kind of pack, ids of the weights and biases) -> (weakrefs to them, their (data_ptr, _version)s, pack, bias)
+_CONV_PACKS = {}
 
 
-def _conv_pack(convs):
-    """(pack, bias) of one launch's Conv2d modules (their weights stacked along cout), cached with
-    gru._gru_pack's scheme: keyed by the parameters' ids, held by weak references, together with
-    the (data_ptr, _version)s they were made from, so another module's tensors never see this
-    pack and an in-place update re-packs."""
-    ts = tuple(c.weight for c in convs) + tuple(c.bias for c in convs)
-    ids = tuple(id(t) for t in ts)
+def _cached_pack(kind, ts, what, make):
+    """`make()`'s (pack, bias) for the parameter tensors `ts`, cached with gru._gru_pack's scheme:
+    keyed by the kind of pack and the parameters' ids, held by weak references, together with the
+    (data_ptr, _version)s they were made from, so another module's tensors never see this pack and
+    an in-place update re-packs."""
+    ids = (kind,) + tuple(id(t) for t in ts)
     key = tuple((t.data_ptr(), t._version) for t in ts)
     ent = _CONV_PACKS.get(ids)
     if ent is None or any(r() is not t for r, t in zip(ent[0], ts)) or ent[1] != key:
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("update_block: the convolution weights must be packed before a graph capture "
+            raise RuntimeError(f"update_block: {what} must be packed before a graph capture "
                                "(run one forward outside the capture first)")
         drop = lambda _r, ids=ids: _CONV_PACKS.pop(ids, None)
-        bias = torch.cat([c.bias.detach().float() for c in convs]).contiguous()
-        ent = (tuple(weakref.ref(t, drop) for t in ts), key, _lib.conv_pack_weights([c.weight for c in convs]), bias)
+        pack, bias = make()
+        ent = (tuple(weakref.ref(t, drop) for t in ts), key, pack, bias)
         _CONV_PACKS[ids] = ent
     return ent[2], ent[3]
+
+
+def _conv_pack(convs):
+    """(pack, bias) of one launch's Conv2d modules (their weights stacked along cout)."""
+    ts = tuple(c.weight for c in convs) + tuple(c.bias for c in convs)
+    return _cached_pack("conv", ts, "the convolution weights",
+                        lambda: (_lib.conv_pack_weights([c.weight for c in convs]),
+                                 torch.cat([c.bias.detach().float() for c in convs]).contiguous()))
+
+
+def _flow_enc_pack(conv):
+    """(pack, bias) of the 7x7 flow convolution."""
+    return _cached_pack("flow_enc", (conv.weight, conv.bias), "the flow convolution's weights",
+                        lambda: (_lib.flow_enc_pack_weights(conv.weight),
+                                 conv.bias.detach().float().contiguous().clone()))
+
+
+def _flow_head_pack(conv):
+    """(pack, bias) of the flow head's second convolution."""
+    return _cached_pack("flow_head", (conv.weight, conv.bias), "the flow head's weights",
+                        lambda: (_lib.flow_head_pack_weights(conv.weight),
+                                 conv.bias.detach().float().contiguous().clone()))
 
 
 def _conv(name, convs, x, out, off):
@@ -54,30 +78,90 @@ def _conv(name, convs, x, out, off):
             off += c.out_channels
 
 
-def update_block(module, net, inp, corr, flow, fused=False, defer_mask=False):
+class UpdateWorkspace:
+    """The buffers update_block fills, kept across the refinement iterations of one forward:
+    f1 = relu(convf1(flow)), cf = [convc2 | convf2], x = [inp | conv | flow] (the GRU input; `inp`
+    is copied into it here, once), hd = [flow_head.conv1 | mask[0]], and two (coords, flow) pairs
+    that the coordinate update alternates between, since it cannot run in place."""
+
+    def __init__(self, inp):
+        B, _, H, W = inp.shape
+        new = lambda c: torch.empty((B, c, H, W), dtype=torch.float32, device=inp.device)
+        self.f1, self.cf, self.x, self.hd = new(128), new(256), new(256), new(512)
+        self.x[:, :128].copy_(inp)
+        self._new, self._pairs, self._last = new, None, 1
+
+    def coords_pair(self, *inputs):
+        """The (coords_out, flow_out) buffers of the next update: the pair not written last, which
+        none of `inputs` (this update's coordinates and flow) can be."""
+        if self._pairs is None:
+            self._pairs = tuple((self._new(2), self._new(2)) for _ in range(2))
+        k = 1 - self._last
+        taken = {t.data_ptr() for t in inputs}
+        if any(b.data_ptr() in taken for b in self._pairs[k]):
+            k = 1 - k
+        self._last = k
+        return self._pairs[k]
+
+
+def update_block(module, net, inp, corr, flow, fused=False, defer_mask=False, workspace=None, coords1=None,
+                 coords0=None):
     """BasicUpdateBlock.forward (update.py:85-107) for `module`: net, inp [B, 128, H, W], corr the
     lookup [B, 324, H, W] (or relu(convc1(lookup)) [B, 256, H, W] when `fused`), flow
     [B, 2, H, W]; fp32 on the GPU.  Returns (net, mask, delta_flow); with `defer_mask`
     (net, hidden, delta_flow), where hidden = relu(mask[0](net)) is the view of channels 256 .. 511
     of the stacked heads' buffer (hidden._base is that buffer, so upsample.mask_upsample reads it
-    in place at offset 256) and mask[2] is left to the caller."""
+    in place at offset 256) and mask[2] is left to the caller.
+
+    `workspace` (an UpdateWorkspace made from this forward's `inp`) keeps the buffers across
+    iterations; without one they are allocated here.  With `coords1` [B, 2, H, W] the result grows
+    to (net, mask, delta_flow, coords_out, flow_out): coords_out = coords1 + delta_flow and, with
+    `coords0`, flow_out = coords_out - coords0 (else None), in buffers of the workspace that the
+    call after the next one overwrites."""
     for t, nm in ((net, "net"), (inp, "inp"), (corr, "corr"), (flow, "flow")):
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
             raise RuntimeError(f"{nm} must be a tensor on an MI355X (HIP) device: eraft_amd has no CPU fallback")
+    if coords0 is not None and coords1 is None:
+        raise ValueError("coords0 needs coords1")
     enc = module.encoder
     net, inp, corr, flow = (t.detach() for t in (net, inp, corr, flow))
-    B, _, H, W = net.shape
+    ws = workspace if workspace is not None else UpdateWorkspace(inp)
+    if tuple(ws.x.shape) != (net.shape[0], 256, *net.shape[2:]) or ws.x.device != net.device:
+        raise ValueError(f"workspace was made for {tuple(ws.x.shape)} on {ws.x.device}, net is {tuple(net.shape)} "
+                         f"on {net.device}")
     c1 = (corr if fused else F.relu(enc.convc1(corr))).contiguous()
-    cf = torch.empty((B, 256, H, W), dtype=torch.float32, device=net.device)  # [convc2 | convf2]
+    cf, x, hd = ws.cf, ws.x, ws.hd
     _conv("convc2", (enc.convc2,), c1, cf, 0)
-    _conv("convf2", (enc.convf2,), F.relu(enc.convf1(flow)).contiguous(), cf, 192)
-    x = torch.empty((B, 256, H, W), dtype=torch.float32, device=net.device)   # [inp | conv | flow]
-    x[:, :128].copy_(inp)
-    x[:, 254:].copy_(flow)
+    flow = flow.contiguous()
+    if USE_KERNEL["convf1"]:
+        packed, bias = _flow_enc_pack(enc.convf1)
+        _lib.flow_enc_forward(flow, packed, bias, 128, True, out=ws.f1, flow_copy=x, copy_offset=254)
+    else:
+        ws.f1.copy_(F.relu(enc.convf1(flow)))
+        x[:, 254:].copy_(flow)
+    _conv("convf2", (enc.convf2,), ws.f1, cf, 192)
     _conv("conv", (enc.conv,), cf, x, 128)
     net = module.gru(net.contiguous(), x)
-    hd = torch.empty((B, 512, H, W), dtype=torch.float32, device=net.device)  # [flow_head.conv1 | mask[0]]
     _conv("heads", (module.flow_head.conv1, module.mask[0]), net.contiguous(), hd, 0)
-    if defer_mask:
-        return net, hd[:, 256:], module.flow_head.conv2(hd[:, :256])
-    return net, 0.25 * module.mask[2](hd[:, 256:]), module.flow_head.conv2(hd[:, :256])
+    head2 = module.flow_head.conv2
+    coords_out = flow_out = None
+    if coords1 is not None:
+        coords1 = coords1.detach().contiguous()
+        coords0 = None if coords0 is None else coords0.detach().contiguous()
+        coords_out, flow_out = ws.coords_pair(coords1, flow, *(() if coords0 is None else (coords0,)))
+        if coords0 is None:
+            flow_out = None
+    if USE_KERNEL["flow_head2"]:
+        packed, bias = _flow_head_pack(head2)
+        delta = _lib.flow_head_forward(hd, 0, packed, bias, coords_in=coords1, coords0=coords0,
+                                       coords_out=coords_out, flow_out=flow_out)[0]
+    else:
+        delta = head2(hd[:, :256])
+        if coords1 is not None:
+            torch.add(coords1, delta, out=coords_out)
+            if coords0 is not None:
+                torch.sub(coords_out, coords0, out=flow_out)
+    mask = hd[:, 256:] if defer_mask else 0.25 * module.mask[2](hd[:, 256:])
+    if coords1 is None:
+        return net, mask, delta
+    return net, mask, delta, coords_out, flow_out

@@ -67,7 +67,9 @@ extern "C" {
  *        Added under 202 (purely additive, no version change): corr_ondemand_workspace,
  *        corr_ondemand_prepare, corr_ondemand_lookup; corr_ondemand_bwd_workspace,
  *        corr_ondemand_backward; corr_mask_upsample_weights_bytes,
- *        corr_mask_upsample_pack_weights, corr_mask_upsample_forward. */
+ *        corr_mask_upsample_pack_weights, corr_mask_upsample_forward; corr_flow_enc_weights_bytes,
+ *        corr_flow_enc_pack_weights, corr_flow_enc_forward, corr_flow_head_weights_bytes,
+ *        corr_flow_head_pack_weights, corr_flow_head_forward. */
 int corr_version(void);
 
 /* Thread-local description of the last error on this thread ("" if none). */
@@ -687,6 +689,78 @@ int corr_mask_upsample_pack_weights(const float *w, void *packed, void *stream);
 int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
                                const void *packed, const float *bias, float mask_scale, int B, int H, int W,
                                float *out, void *stream);
+
+/*
+ * The update block's tail (model/update.py:63-82 BasicMotionEncoder.convf1, :20-31 FlowHead.conv2,
+ * and the coordinate update of model/eraft.py's refinement loop), inference only.
+ *
+ * corr_flow_enc_forward: the 7x7 convolution of the 2-channel flow at stride 1 with zero padding
+ * 3, bias and an optional ReLU (relu = 1), written into a channel window of `out`:
+ *   out[b][out_offset + o][y][x] = act(bias[o] + sum_c sum_ky sum_kx w[o][c][ky][kx] * flow[b][c][y + ky - 3][x + kx - 3])
+ * flow is [B][2][H][W]; out is [B][out_channels][H][W], of which exactly channels out_offset ..
+ * out_offset + cout - 1 are written.  Maps smaller than the window (1 x 1, 3 x 4) are allowed.
+ * Pass-through: with flow_copy not NULL the launch also writes flow[b][c], bit for bit, into
+ * channels copy_offset, copy_offset + 1 of the [B][copy_channels][H][W] tensor flow_copy (the flow
+ * channels of the GRU input), and nothing else of it.  out and flow_copy must not overlap flow;
+ * they may be one tensor (same pointer, same channel count) written through disjoint channel
+ * windows, and must not overlap each other in any other way.
+ * Weights: w is a contiguous Conv2d weight [cout][2][7][7], split once per weight version by
+ * corr_flow_enc_pack_weights into a corr_flow_enc_weights_bytes(cout) buffer (16-B aligned,
+ * opaque; 0 for unsupported sizes).  The pack holds the rows padded with zeros to a multiple of
+ * 64; padding rows are never stored.  bias is [cout], or NULL for no bias.
+ * Arithmetic: corr_conv_forward's (the bf16 MFMA with the exact three-piece split, six products
+ * per fp32 product in its order, no scales: no narrower than fp32).  K order: tap-major, tap =
+ * 7 ky + kx ascending, the two channels of a tap adjacent (k = 2 tap + c), K = 98 padded with zero
+ * weights to 128: four K steps of 16 taps; then + bias, then the ReLU, each fp32 op rounded once.
+ * Deterministic.  Non-finite inputs are NOT parity-checked.
+ * Sizes: 1 <= cout <= 1024, otherwise CORR_EUNSUPPORTED (and a size of 0); any B, H, W >= 1 with
+ * B*H*W < 2^31.  CORR_EINVAL: a NULL flow, packed or out (pack: w, packed); relu not 0 or 1;
+ * out_offset < 0 or out_offset + cout > out_channels; with flow_copy, copy_offset < 0 or
+ * copy_offset + 2 > copy_channels; packed not 16-byte aligned; B, H or W < 1 or B*H*W >= 2^31;
+ * out or flow_copy overlapping flow, or each other as described above.
+ *
+ * corr_flow_head_forward: the 3x3 convolution from 256 to 2 channels at stride 1 with zero
+ * padding 1, bias, no ReLU, and the coordinate update:
+ *   delta[b][o][y][x] = bias[o] + sum_c sum_ky sum_kx w[o][c][ky][kx] * hidden[b][hidden_offset + c][y + ky - 1][x + kx - 1]
+ *   coords_out = coords_in + delta            (when coords_in is not NULL)
+ *   flow_out   = coords_out - coords0         (when coords0 is not NULL as well)
+ * hidden is a [B][hidden_channels][H][W] tensor of which channels hidden_offset .. hidden_offset +
+ * 255 are read in place (corr_mask_upsample_forward's convention: the flow half of the update
+ * block's stacked heads buffer needs no copy); bias is [2]; coords_in, coords0, delta, coords_out
+ * and flow_out are [B][2][H][W].  With coords_in NULL only delta is written (coords_out and
+ * flow_out are ignored); with coords0 NULL flow_out is ignored.  The two updates are one fp32
+ * operation each, rounded once, on the delta this launch stores.  No output may overlap hidden,
+ * coords_in, coords0 or another output: a workgroup reads its neighbours' pixels, so there is no
+ * in-place update (callers keep two coordinate buffers).
+ * Weights: w is a contiguous Conv2d weight [2][256][3][3], split once per weight version by
+ * corr_flow_head_pack_weights into a corr_flow_head_weights_bytes() buffer (16-B aligned, opaque).
+ * Arithmetic and K order (NOT corr_conv_forward's): per pixel and tap = 3 ky + kx the product
+ *   P[o][tap] = sum_c w[o][c][tap] * hidden[c]
+ * is accumulated over ascending 32-channel steps on the bf16 MFMA with the exact three-piece split
+ * (six products per fp32 product in corr_conv_forward's order); a pixel outside the map has P = 0.
+ * Then delta = ((..(P[o][0] + P[o][1]) + ..) + P[o][8]) + bias[o], each P taken at its tap's
+ * neighbour, taps ascending, each fp32 op rounded once.  Deterministic.  Non-finite inputs are
+ * NOT parity-checked.
+ * Sizes: any B, H, W >= 1 with B*H*W < 2^31.  CORR_EINVAL: a NULL hidden, packed, bias or delta
+ * (pack: w, packed); coords0 given without coords_in; coords_out NULL with coords_in given;
+ * flow_out NULL with coords0 given; hidden_offset < 0 or hidden_offset + 256 > hidden_channels;
+ * packed not 16-byte aligned; B, H or W < 1 or B*H*W >= 2^31; an output overlapping an input or
+ * another output.
+ *
+ * Both: all tensors fp32, 4-byte aligned.  Every refusal comes before any HIP call.  No workspace,
+ * no allocation, no synchronisation; each is one launch on `stream` and can be captured into a
+ * graph.
+ */
+size_t corr_flow_enc_weights_bytes(int cout);
+int corr_flow_enc_pack_weights(const float *w, int cout, void *packed, void *stream);
+int corr_flow_enc_forward(const float *flow, int B, int H, int W, const void *packed, const float *bias, int cout,
+                          int relu, float *out, int out_channels, int out_offset, float *flow_copy,
+                          int copy_channels, int copy_offset, void *stream);
+size_t corr_flow_head_weights_bytes(void);
+int corr_flow_head_pack_weights(const float *w, void *packed, void *stream);
+int corr_flow_head_forward(const float *hidden, int hidden_channels, int hidden_offset, int B, int H, int W,
+                           const void *packed, const float *bias, const float *coords_in, const float *coords0,
+                           float *delta, float *coords_out, float *flow_out, void *stream);
 
 #ifdef __cplusplus
 }

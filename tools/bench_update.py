@@ -6,10 +6,16 @@ Per size:
   (a) each of the four launches (convc2, convf2, conv, the stacked heads) against the torch ops it
       replaces: conv + bias + ReLU and the cat it removes (convf2 carries cat([c, f]); conv carries
       cat([out, flow]) and cat([inp, motion]) on the torch side and the copies of inp and flow
-      into the GRU input on the kernel side);
+      into the GRU input on the kernel side); and the tail's two launches: convf1
+      (corr_flow_enc_forward against conv + ReLU + .contiguous() + the flow's copy) and flow_head2
+      (corr_flow_head_forward against the conv + coords1 + delta + coords1 - coords0, and against
+      corr_conv_forward with cout = 2 on a contiguous copy of the hidden half plus the same two
+      torch ops, "conv_kernel");
   (b) one whole BasicUpdateBlock call (lookup already through convc1, the GRU by its own switch)
       with the switch off, with every convolution on the kernel ("all"), and with the committed
-      table update.USE_KERNEL ("fused").
+      table update.USE_KERNEL ("fused"); then one refinement iteration's worth, the block plus the
+      coordinate update: on torch ("iter_torch"), on the kernels without the tail ("iter_no_tail")
+      and with the tail, a workspace and the update in the flow head's launch ("iter_tail").
 Median / min / max ms per call over the trial windows, and the kernel's norm-relative error
 against an fp64 CPU run.  Prints one JSON document; --json also writes it to a file."""
 import argparse
@@ -126,13 +132,77 @@ def bench_size(name, trials, dev):
         res["launches"][lname] = r
         del gt, gk, kt, kk
 
-    # (b) the whole block
+    # (a) continued: the tail's two launches (corr_flow.hip), each against the torch ops it replaces
+    hd = torch.relu(rnd(512))
+    coords0 = torch.stack(torch.meshgrid(torch.arange(W, device=dev, dtype=torch.float32),
+                                         torch.arange(H, device=dev, dtype=torch.float32), indexing="xy"))
+    coords0 = coords0[None].repeat(B, 1, 1, 1).contiguous()
+    coords1 = coords0 + flow
+    head2 = m.flow_head.conv2
+    f1b, hcopy = buf(128), hd[:, :256].contiguous()
+
+    def torch_convf1():
+        xb[:, 254:].copy_(flow)
+        return F.relu(enc.convf1(flow)).contiguous()
+
+    def kernel_convf1():
+        packed, bias = update._flow_enc_pack(enc.convf1)
+        return _lib.flow_enc_forward(flow, packed, bias, 128, True, out=f1b, flow_copy=xb, copy_offset=254)
+
+    def torch_head2():
+        d = head2(hd[:, :256])
+        c = coords1 + d
+        return d, c, c - coords0
+
+    def kernel_head2():
+        packed, bias = update._flow_head_pack(head2)
+        return _lib.flow_head_forward(hd, 0, packed, bias, coords_in=coords1, coords0=coords0)
+
+    def conv_head2():  # the cheapest alternative already in the library: corr_conv_forward with cout = 2
+        packed, bias = update._conv_pack((head2,))
+        d = _lib.conv_forward(hcopy, None, packed, bias, 2, False)
+        c = coords1 + d
+        return d, c, c - coords0
+
+    with torch.no_grad():
+        ref_f1 = F.relu(F.conv2d(flow.cpu().double(), enc.convf1.weight.cpu().double(), enc.convf1.bias.cpu().double(),
+                                 padding=3))
+        ref_d = F.conv2d(hd[:, :256].cpu().double(), head2.weight.cpu().double(), head2.bias.cpu().double(), padding=1)
+    for lname, fns, ref in (("convf1", {"torch": torch_convf1, "kernel": kernel_convf1}, ref_f1),
+                            ("flow_head2", {"torch": torch_head2, "kernel": kernel_head2, "conv_kernel": conv_head2},
+                             ref_d)):
+        caps = {n: capture(fn, stream) for n, fn in fns.items()}
+        r = alternate({n: cp[0] for n, cp in caps.items()}, trials, steps)
+        for n, cp in caps.items():
+            o = cp[1][0] if isinstance(cp[1], tuple) else cp[1]
+            r[n]["rel_err_vs_fp64"] = norm_rel(o.cpu(), ref)
+        r["kernel_over_torch"] = round(r["kernel"]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
+        if "conv_kernel" in r:
+            r["kernel_over_conv_kernel"] = round(r["kernel"]["call_ms_median"] / r["conv_kernel"]["call_ms_median"], 3)
+        res["launches"][lname] = r
+        del caps
+
+    # (b) the whole block, then one iteration's worth of it: the block and the coordinate update, on
+    # torch, on the kernels without the tail ("no_tail": convf1 and flow_head2 on torch, fresh
+    # buffers, torch's coords1 + delta and coords1 - coords0) and on the tail with a workspace
     table = dict(update.USE_KERNEL)
+    no_tail = dict(table, convf1=False, flow_head2=False)
+    ws = update.UpdateWorkspace(inp)
+
+    def plain_iter():
+        out = m(net, inp, c1, flow, True)
+        c = coords1 + out[2]
+        return out + (c, c - coords0)
+
     graphs, outs, keep = {}, {}, []
-    for vname, on, tab in (("torch", False, table), ("all", True, dict.fromkeys(table, True)), ("fused", True, table)):
+    for vname, on, tab, fn in (
+            ("torch", False, table, None), ("all", True, dict.fromkeys(table, True), None), ("fused", True, table, None),
+            ("iter_torch", False, table, plain_iter), ("iter_no_tail", True, no_tail, plain_iter),
+            ("iter_tail", True, table, lambda: m(net, inp, c1, flow, True, workspace=ws, coords1=coords1,
+                                                 coords0=coords0))):
         BasicUpdateBlock.fused = on
         update.USE_KERNEL.update(tab)
-        graphs[vname], outs[vname], k = capture(lambda: m(net, inp, c1, flow, True), stream)
+        graphs[vname], outs[vname], k = capture(fn or (lambda: m(net, inp, c1, flow, True)), stream)
         keep.append(k)
     BasicUpdateBlock.fused = False
     update.USE_KERNEL.update(table)
@@ -146,6 +216,8 @@ def bench_size(name, trials, dev):
     r["gru_fused"] = bool(type(m.gru).fused)
     r["fused_over_torch"] = round(r["fused"]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
     r["all_over_torch"] = round(r["all"]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
+    r["iter_tail_over_iter_no_tail"] = round(r["iter_tail"]["call_ms_median"] / r["iter_no_tail"]["call_ms_median"], 3)
+    r["iter_tail_over_iter_torch"] = round(r["iter_tail"]["call_ms_median"] / r["iter_torch"]["call_ms_median"], 3)
     res["block"] = r
     del graphs, keep
     torch.cuda.empty_cache()
