@@ -527,6 +527,34 @@ int corr_lookup_conv_bwd(const float *const *pyr, const float *coords, int B, in
                       fn);
 }
 
+// ---- checks shared by the bf16x6 convolution entry points.  The order of an entry point's checks
+// decides which error a caller sees, so each call stands where the test it replaces stood. ----
+// A pack: not NULL (an entry point that tests that earlier keeps its check_ptr there) and aligned
+// for the kernels' 16-byte loads.
+static int check_packed(const char *fn, const void *packed) {
+    const int rc = check_ptr(fn, packed, "packed");
+    if (rc || (uintptr_t)packed % 16 == 0) return rc;
+    return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+}
+static int check_pixels(const char *fn, int B, int H, int W) {  // pixels and tiles are int-indexed
+    return (long long)B * H * W > (1LL << 31) - 1 ? fail(CORR_EINVAL, "%s: B*H*W too large", fn) : CORR_OK;
+}
+static int check_opt_ptr(const char *fn, const void *p, const char *name) {
+    return p ? check_ptr(fn, p, name) : CORR_OK;
+}
+// Channels off .. off + n - 1 of a tensor with `channels` of them; n is an argument of the entry
+// point (n_name) or a constant of the kernel.
+static int check_window(const char *fn, const char *off_name, int off, int n, const char *ch_name, int channels,
+                        const char *n_name = nullptr) {
+    if (off >= 0 && (long long)off + n <= channels) return CORR_OK;
+    char last[64], got[32] = "";
+    if (n_name) snprintf(got, sizeof got, "%s = %d, ", n_name, n);
+    if (n_name) snprintf(last, sizeof last, " .. %s + %s - 1", off_name, n_name);
+    else snprintf(last, sizeof last, n == 2 ? ", %s + %d" : " .. %s + %d", off_name, n - 1);
+    return fail(CORR_EINVAL, "%s: channels %s%s must lie in [0, %s) (got %s = %d, %s%s = %d)", fn, off_name, last,
+                ch_name, off_name, off, got, ch_name, channels);
+}
+
 static int check_gru_channels(const char *fn, int hidden, int input) {
     if (!gru_supported(hidden, input))
         return fail(CORR_EUNSUPPORTED,
@@ -547,9 +575,8 @@ int corr_gru_pack_weights(const float *wz, const float *wr, const float *wq, int
     int rc;
     if ((rc = check_gru_channels(fn, hidden, input))) return rc;
     if ((rc = check_ptr(fn, wz, "wz")) || (rc = check_ptr(fn, wr, "wr")) || (rc = check_ptr(fn, wq, "wq")) ||
-        (rc = check_ptr(fn, packed, "packed")))
+        (rc = check_packed(fn, packed)))
         return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
     return hip_status(launch_gru_pack(wz, wr, wq, hidden, input, packed, (hipStream_t)stream), fn);
 }
 
@@ -563,16 +590,15 @@ int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int in
                        size_t workspace_bytes, float *h_out, void *stream) {
     static const char *fn = "corr_gru_half_step";
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
-    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    int rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if ((rc = check_gru_channels(fn, hidden, input))) return rc;
     if (dir != 0 && dir != 1) return fail(CORR_EINVAL, "%s: dir must be 0 (1x5) or 1 (5x1) (got %d)", fn, dir);
     if ((rc = check_ptr(fn, h, "h")) || (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, bz, "bz")) ||
         (rc = check_ptr(fn, br, "br")) || (rc = check_ptr(fn, bq, "bq")) || (rc = check_ptr(fn, h_out, "h_out")))
         return rc;
     if (input > 0 && (rc = check_ptr(fn, x, "x"))) return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_packed(fn, packed))) return rc;
     if (h_out == h || h_out == x) return fail(CORR_EINVAL, "%s: h_out must not alias h or x", fn);
     const size_t need = gru_workspace(B, hidden, H, W);
     if (!workspace || workspace_bytes < need)
@@ -602,8 +628,7 @@ int corr_conv_pack_weights(const float *w, int cout, int cin, void *packed, void
     g_err[0] = 0;
     int rc;
     if ((rc = check_conv_channels(fn, cout, cin, 0))) return rc;
-    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_conv_pack(w, cout, cin, packed, (hipStream_t)stream), fn);
 }
 
@@ -618,25 +643,21 @@ int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int 
                       void *stream) {
     static const char *fn = "corr_conv_forward";
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
-    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    int rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if ((rc = check_conv_channels(fn, cout, ca, cb))) return rc;
     if (relu != 0 && relu != 1) return fail(CORR_EINVAL, "%s: relu must be 0 or 1 (got %d)", fn, relu);
-    if (out_offset < 0 || (long long)out_offset + cout > out_channels)
-        return fail(CORR_EINVAL, "%s: channels out_offset .. out_offset + cout - 1 must lie in [0, out_channels) "
-                                 "(got out_offset = %d, cout = %d, out_channels = %d)",
-                    fn, out_offset, cout, out_channels);
+    if ((rc = check_window(fn, "out_offset", out_offset, cout, "out_channels", out_channels, "cout"))) return rc;
     if ((rc = check_ptr(fn, in_a, "in_a")) || (rc = check_ptr(fn, packed, "packed")) ||
         (rc = check_ptr(fn, out, "out")))
         return rc;
     if (cb > 0 && (rc = check_ptr(fn, in_b, "in_b"))) return rc;
-    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    if ((rc = check_opt_ptr(fn, bias, "bias"))) return rc;
     const long double px = (long double)B * H * W * sizeof(float), ob = px * out_channels;
     if (ob > (long double)(SIZE_MAX / 2)) return fail(CORR_EINVAL, "%s: B*out_channels*H*W too large", fn);
     if (ranges_overlap(out, ob, in_a, px * ca) || (cb > 0 && ranges_overlap(out, ob, in_b, px * cb)))
         return fail(CORR_EINVAL, "%s: out must not overlap in_a or in_b", fn);
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_conv_forward(in_a, ca, in_b, cb, B, H, W, packed, bias, cout, relu, out, out_channels,
                                           out_offset, (hipStream_t)stream),
                       fn);
@@ -652,15 +673,14 @@ int corr_enc_conv_forward(const float *in, int cin, int B, int H, int W, int str
                           int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
     static const char *fn = "corr_enc_conv_forward";
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
-    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    int rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if (stride != 1 && stride != 2)
         return fail(CORR_EUNSUPPORTED, "%s: built for stride 1 and 2 (got %d)", fn, stride);
     if ((rc = check_conv_channels(fn, cout, cin, 0))) return rc;
     if ((rc = check_ptr(fn, in, "in")) || (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, out, "out")))
         return rc;
-    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    if ((rc = check_opt_ptr(fn, bias, "bias"))) return rc;
     if (!in_scale != !in_shift)
         return fail(CORR_EINVAL, "%s: in_scale and in_shift must both be given or both be NULL", fn);
     if (in_scale && ((rc = check_ptr(fn, in_scale, "in_scale")) || (rc = check_ptr(fn, in_shift, "in_shift"))))
@@ -672,7 +692,7 @@ int corr_enc_conv_forward(const float *in, int cin, int B, int H, int W, int str
         if (stats_bytes < need)
             return fail(CORR_EINVAL, "%s: stats of %zu bytes needed, got %zu", fn, need, stats_bytes);
     }
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_packed(fn, packed))) return rc;
     const long double ib = (long double)B * H * W * sizeof(float) * cin;
     const long double ob = (long double)B * Ho * Wo * sizeof(float) * cout;
     if (ranges_overlap(out, ob, in, ib)) return fail(CORR_EINVAL, "%s: out must not overlap in", fn);
@@ -736,8 +756,7 @@ int corr_enc_stem_pack_weights(const float *w, int cout, int cin, void *packed, 
     g_err[0] = 0;
     int rc;
     if ((rc = check_stem_channels(fn, cout, cin))) return rc;
-    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_enc_stem_pack(w, cout, cin, packed, (hipStream_t)stream), fn);
 }
 
@@ -749,7 +768,7 @@ static int check_enc_front(const char *fn, const float *in, int cin, int B, int 
     int rc;
     if ((rc = check_ptr(fn, in, "in")) || (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, out, "out")))
         return rc;
-    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    if ((rc = check_opt_ptr(fn, bias, "bias"))) return rc;
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     if (stats) {
         if ((rc = check_ptr(fn, stats, "stats"))) return rc;
@@ -760,7 +779,7 @@ static int check_enc_front(const char *fn, const float *in, int cin, int B, int 
     const long double ib = (long double)B * H * W * sizeof(float) * cin;
     const long double ob = (long double)B * Ho * Wo * sizeof(float) * cout;
     if (ranges_overlap(out, ob, in, ib)) return fail(CORR_EINVAL, "%s: out must not overlap in", fn);
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_packed(fn, packed))) return rc;
     return CORR_OK;
 }
 
@@ -768,9 +787,8 @@ int corr_enc_stem_forward(const float *in, int cin, int B, int H, int W, const v
                           int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
     static const char *fn = "corr_enc_stem_forward";
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
-    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    int rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if ((rc = check_stem_channels(fn, cout, cin))) return rc;
     if ((rc = check_enc_front(fn, in, cin, B, H, W, 2, packed, bias, cout, out, stats, stats_bytes))) return rc;
     return hip_status(launch_enc_stem(in, cin, B, H, W, packed, bias, cout, out, static_cast<float *>(stats),
@@ -796,8 +814,7 @@ int corr_enc_pw_pack_weights(const float *w, int cout, int cin, void *packed, vo
     g_err[0] = 0;
     int rc;
     if ((rc = check_pw_channels(fn, cout, cin))) return rc;
-    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_enc_pw_pack(w, cout, cin, packed, (hipStream_t)stream), fn);
 }
 
@@ -805,9 +822,8 @@ int corr_enc_pw_forward(const float *in, int cin, int B, int H, int W, int strid
                         const float *bias, int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
     static const char *fn = "corr_enc_pw_forward";
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
-    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    int rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if (stride != 1 && stride != 2)
         return fail(CORR_EUNSUPPORTED, "%s: built for stride 1 and 2 (got %d)", fn, stride);
     if ((rc = check_pw_channels(fn, cout, cin))) return rc;
@@ -857,8 +873,7 @@ int corr_mask_upsample_pack_weights(const float *w, void *packed, void *stream) 
     static const char *fn = "corr_mask_upsample_pack_weights";
     g_err[0] = 0;
     int rc;
-    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_mask_upsample_pack(w, packed, (hipStream_t)stream), fn);
 }
 
@@ -869,10 +884,7 @@ int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hid
     g_err[0] = 0;
     int rc = check_dims(fn, B, 1, H, W, 1);
     if (rc) return rc;
-    if (hidden_offset < 0 || (long long)hidden_offset + 256 > hidden_channels)
-        return fail(CORR_EINVAL, "%s: channels hidden_offset .. hidden_offset + 255 must lie in [0, hidden_channels) "
-                                 "(got hidden_offset = %d, hidden_channels = %d)",
-                    fn, hidden_offset, hidden_channels);
+    if ((rc = check_window(fn, "hidden_offset", hidden_offset, 256, "hidden_channels", hidden_channels))) return rc;
     if ((rc = check_ptr(fn, hidden, "hidden")) || (rc = check_ptr(fn, flow, "flow")) ||
         (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, bias, "bias")) ||
         (rc = check_ptr(fn, out, "out")))
@@ -883,7 +895,7 @@ int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hid
         return fail(CORR_EINVAL, "%s: B*hidden_channels*H*W too large", fn);
     if (ranges_overlap(out, ob, hidden, px * hidden_channels) || ranges_overlap(out, ob, flow, px * 2))
         return fail(CORR_EINVAL, "%s: out must not overlap hidden or flow", fn);
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_mask_upsample(hidden, hidden_channels, hidden_offset, flow, packed, bias, mask_scale, B,
                                            H, W, out, (hipStream_t)stream),
                       fn);
@@ -905,8 +917,7 @@ int corr_flow_enc_pack_weights(const float *w, int cout, void *packed, void *str
     g_err[0] = 0;
     int rc;
     if ((rc = check_flow_enc_channels(fn, cout))) return rc;
-    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_flow_enc_pack(w, cout, packed, (hipStream_t)stream), fn);
 }
 
@@ -915,28 +926,21 @@ int corr_flow_enc_forward(const float *flow, int B, int H, int W, const void *pa
                           int copy_channels, int copy_offset, void *stream) {
     static const char *fn = "corr_flow_enc_forward";
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
-    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
+    int rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if ((rc = check_flow_enc_channels(fn, cout))) return rc;
     if (relu != 0 && relu != 1) return fail(CORR_EINVAL, "%s: relu must be 0 or 1 (got %d)", fn, relu);
-    if (out_offset < 0 || (long long)out_offset + cout > out_channels)
-        return fail(CORR_EINVAL, "%s: channels out_offset .. out_offset + cout - 1 must lie in [0, out_channels) "
-                                 "(got out_offset = %d, cout = %d, out_channels = %d)",
-                    fn, out_offset, cout, out_channels);
+    if ((rc = check_window(fn, "out_offset", out_offset, cout, "out_channels", out_channels, "cout"))) return rc;
     if ((rc = check_ptr(fn, flow, "flow")) || (rc = check_ptr(fn, packed, "packed")) ||
         (rc = check_ptr(fn, out, "out")))
         return rc;
-    if (bias && (rc = check_ptr(fn, bias, "bias"))) return rc;
+    if ((rc = check_opt_ptr(fn, bias, "bias"))) return rc;
     const long double px = (long double)B * H * W * sizeof(float), ob = px * out_channels;
     if (ob > (long double)(SIZE_MAX / 2)) return fail(CORR_EINVAL, "%s: B*out_channels*H*W too large", fn);
     if (ranges_overlap(out, ob, flow, px * 2)) return fail(CORR_EINVAL, "%s: out must not overlap flow", fn);
     if (flow_copy) {
         if ((rc = check_ptr(fn, flow_copy, "flow_copy"))) return rc;
-        if (copy_offset < 0 || (long long)copy_offset + 2 > copy_channels)
-            return fail(CORR_EINVAL, "%s: channels copy_offset, copy_offset + 1 must lie in [0, copy_channels) "
-                                     "(got copy_offset = %d, copy_channels = %d)",
-                        fn, copy_offset, copy_channels);
+        if ((rc = check_window(fn, "copy_offset", copy_offset, 2, "copy_channels", copy_channels))) return rc;
         const long double cb = px * copy_channels;
         if (cb > (long double)(SIZE_MAX / 2)) return fail(CORR_EINVAL, "%s: B*copy_channels*H*W too large", fn);
         if (ranges_overlap(flow_copy, cb, flow, px * 2))
@@ -950,7 +954,7 @@ int corr_flow_enc_forward(const float *flow, int B, int H, int W, const void *pa
                             fn);
         }
     }
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_flow_enc(flow, B, H, W, packed, bias, cout, relu, out, out_channels, out_offset,
                                       flow_copy, copy_channels, copy_offset, (hipStream_t)stream),
                       fn);
@@ -962,8 +966,7 @@ int corr_flow_head_pack_weights(const float *w, void *packed, void *stream) {
     static const char *fn = "corr_flow_head_pack_weights";
     g_err[0] = 0;
     int rc;
-    if ((rc = check_ptr(fn, w, "w")) || (rc = check_ptr(fn, packed, "packed"))) return rc;
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, w, "w")) || (rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_flow_head_pack(w, packed, (hipStream_t)stream), fn);
 }
 
@@ -972,13 +975,9 @@ int corr_flow_head_forward(const float *hidden, int hidden_channels, int hidden_
                            float *delta, float *coords_out, float *flow_out, void *stream) {
     static const char *fn = "corr_flow_head_forward";
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
-    if ((long long)B * H * W > (1LL << 31) - 1) return fail(CORR_EINVAL, "%s: B*H*W too large", fn);
-    if (hidden_offset < 0 || (long long)hidden_offset + 256 > hidden_channels)
-        return fail(CORR_EINVAL, "%s: channels hidden_offset .. hidden_offset + 255 must lie in [0, hidden_channels) "
-                                 "(got hidden_offset = %d, hidden_channels = %d)",
-                    fn, hidden_offset, hidden_channels);
+    int rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
+    if ((rc = check_window(fn, "hidden_offset", hidden_offset, 256, "hidden_channels", hidden_channels))) return rc;
     if ((rc = check_ptr(fn, hidden, "hidden")) || (rc = check_ptr(fn, packed, "packed")) ||
         (rc = check_ptr(fn, bias, "bias")) || (rc = check_ptr(fn, delta, "delta")))
         return rc;
@@ -1001,7 +1000,7 @@ int corr_flow_head_forward(const float *hidden, int hidden_channels, int hidden_
             if (outs[j] && ranges_overlap(outs[k], cb, outs[j], cb))
                 return fail(CORR_EINVAL, "%s: %s must not overlap %s", fn, names[k], names[j]);
     }
-    if ((uintptr_t)packed % 16) return fail(CORR_EINVAL, "%s: packed is not 16-byte aligned", fn);
+    if ((rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_flow_head(hidden, hidden_channels, hidden_offset, B, H, W, packed, bias, coords_in,
                                        coords0, delta, coords_in ? coords_out : nullptr, coords0 ? flow_out : nullptr,
                                        (hipStream_t)stream),

@@ -55,11 +55,11 @@ __device__ inline float split_sum(float hi, float lo) { return __builtin_isinf(h
 // on exact three-piece bf16 splits into ONE accumulator, so an infinite operand element meets
 // zero pieces of the other operand (inf * 0 = NaN) and every output it reaches comes out NaN
 // where the reference's fp32 matmul gives +-inf (autograd of model/corr.py:58-60).  The split-K
-// reduce (and the direct epilogue) therefore recompute exactly the outputs that came out NaN as
-// the reference does — dmatmul = dC / sqrt(D) elementwise, then a plain fp32 dot product — so
-// NaN stays NaN where fp32 has one (a NaN operand, inf * 0, opposite infinities) and the rest
-// become fp32's +-inf.  Finite inputs never reach it (no NaN), so their bits are unchanged.
-// K = 0: off (the fp32-operand and f16x3 GEMMs).
+// reduce therefore recomputes exactly the outputs that came out NaN as the reference does —
+// dmatmul = dC / sqrt(D) elementwise, then a plain fp32 dot product — so NaN stays NaN where fp32
+// has one (a NaN operand, inf * 0, opposite infinities) and the rest become fp32's +-inf.  Finite
+// inputs never reach it (no NaN), so their bits are unchanged.  K = 0: off (the fp32-operand and
+// f16x3 GEMMs).
 struct NanFix {
     const float *A = nullptr, *Bm = nullptr;
     long a_sb = 0, a_sr = 0, b_sb = 0, b_sr = 0, b_sk = 0;

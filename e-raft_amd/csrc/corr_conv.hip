@@ -13,9 +13,9 @@
 // The arithmetic is corr_gru.hip's: the implicit GEMM
 //   out[o][pixel] = sum_chunk sum_tap sum_{c in chunk} W[o][c][tap] * in[c][pixel + tap offset]
 // with K = 9 cin in steps of 32 channels (channel chunk outer, tap inner, ky major and kx minor: a
-// fixed order), on v_mfma_f32_16x16x32_bf16 with the build's exact three-piece split (x = hi +
-// mid + lo, six products per fp32 product in lookup_conv_kernel's order, two accumulators joined
-// by split_sum: no narrower than fp32, no scales).
+// fixed order), on the 16x16x32 bf16 MFMA with the build's exact three-piece split (x = hi +
+// mid + lo, six products per fp32 product in the family's order, corr_bf16x6.h, two accumulators
+// joined by split_sum: no narrower than fp32, no scales).
 //
 // Workgroup = 4 waves = 32 output rows x one tile of 4 rows x 16 columns of one batch item's
 // map; wave w owns rows 16 (w & 1) .. + 16 and tile rows 2 (w >> 1), + 1 (one 16x16 output tile
@@ -43,17 +43,14 @@
 // pieces of the weights); finite inputs give finite outputs.
 #include <type_traits>
 
-#include "corr_build_common.h"
+#include "corr_bf16x6.h"
 #include "corr_common.h"
 
 namespace corr {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kConvTW = 16, kConvTH = 4;       // pixel tile (columns x rows)
+// (the pixel tile kConvTW x kConvTH, kConvNT threads and the packs' row padding kConvPad are the
+// family's: corr_bf16x6.h)
 // The staged window of a 4 x 16 output tile at stride S: S (t - 1) + 3 positions a side.
 template <int S>
 struct ConvGeo {
@@ -72,8 +69,6 @@ struct ConvGeo {
 };
 constexpr int kConvT = 1;                      // 16-row blocks per wave (2 measured slower)
 constexpr int kConvOB = 32 * kConvT;           // output rows per workgroup
-constexpr int kConvPad = 64;                   // the pack pads the rows to a multiple of this
-constexpr int kConvNT = 256;                   // threads
 constexpr int kConvXS = 16 + 4;                // words per LDS position: 16 channel pairs + pad (16-B rows)
 constexpr int kConvTaps = 9;
 constexpr int kConvWaves = 2;                  // waves per SIMD the kernel is compiled for (<= 256 registers)
@@ -84,11 +79,6 @@ static_assert((2 * kConvTaps) % kConvRing == 0 && kConvAhead < kConvRing, "ring 
 static_assert(kConvNT == 256 && ConvGeo<1>::Stage - (ConvGeo<1>::NLD - 1) * kConvNT > 0 &&
                   (ConvGeo<1>::Stage - (ConvGeo<1>::NLD - 1) * kConvNT) % 64 == 0,
               "the guard of the last staging pass is wave-uniform at stride 1");
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                  0, 0, 0);
-}
 
 // w [cout][cin][3][3] fp32 -> pieces [rows/16 blocks][cin/32 chunks][9 taps][hi, mid, lo][64 lanes]
 // in the 16x16x32 A-fragment order: lane = 16 kg + r holds W[16 ob + r][32 chunk + 8 kg + j][tap],
@@ -109,9 +99,7 @@ __global__ __launch_bounds__(64) void conv_pack_kernel(const float *__restrict__
             split3(live ? a : 0.f, live ? b : 0.f, h[j], m[j], lo[j]);
         }
         u32x4 *dst = frag + ((((size_t)ob * NC + ch) * kConvTaps + t) * 3) * 64 + lane;
-        dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-        dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-        dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        store_pieces(dst, h, m, lo);
     }
 }
 
@@ -278,19 +266,9 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
                     xb[c][p] = *reinterpret_cast<const u32x4 *>(
                         &xs[p][STRIDE * ((j0 + c) * kConvPW + fr) + tp][fk]);
 #pragma unroll
-            for (int t = 0; t < kConvT; ++t) {
-                const u32x4 wh = wa[(S0 + tap) % kConvRing][t][0], wm = wa[(S0 + tap) % kConvRing][t][1],
-                            wl = wa[(S0 + tap) % kConvRing][t][2];
+            for (int t = 0; t < kConvT; ++t)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    acs[t][c] = mfma_bf16(wl, xb[c][0], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wh, xb[c][2], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wm, xb[c][1], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wm, xb[c][0], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wh, xb[c][1], acs[t][c]);
-                    acc[t][c] = mfma_bf16(wh, xb[c][0], acc[t][c]);
-                }
-            }
+                for (int c = 0; c < 2; ++c) six(wa[(S0 + tap) % kConvRing][t], xb[c], acc[t][c], acs[t][c]);
         }
         __syncthreads();
     };
@@ -328,12 +306,8 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
                 }
         }
     } else {
-        // Every lane stays (the reductions and the barrier need all of them); a pixel past Ho / Wo
-        // is neither stored nor counted.  Per output row: the 16 columns by 2 tile rows of a wave
-        // are summed by a butterfly over the 16 lanes of a row group (every lane ends with the
-        // same bits: each level adds the same two values in either order), the squared deviations
-        // from that half's mean likewise; the two halves of the tile (waves w and w + 2) meet in
-        // LDS and thread `row` merges them, upper half first (Chan et al.).
+        // A copy of front_epilogue<1, true> (corr_enc_front.hip, where it is described) that writes
+        // the channel window; kept in step with it by hand, see there.
         static_assert(kConvT == 1, "the statistics epilogue is written for one row block per wave");
         float *red = reinterpret_cast<float *>(&xs[0][0][0]);  // [half][32 rows][sum, M2]; the tile is consumed
         const int nx = min(kConvTW, Wo - x0);

@@ -6,12 +6,12 @@
 //   pw:    out[b][o][y][x] = bias[o] + sum_c w[o][c] in[b][c][s y][s x],  s = 1 or 2
 //   join:  out = relu(s(skip) + relu(y * scale + shift)),  s(v) = v * skip_scale + skip_shift [, relu]
 //
-// The arithmetic is corr_conv.hip's: an implicit GEMM on v_mfma_f32_16x16x32_bf16 with the build's
-// exact three-piece split (x = hi + mid + lo, six products per fp32 product in corr_conv.hip's
-// order, two accumulators joined by split_sum), and so are the workgroup's shape (4 waves, one
-// tile of 4 rows x 16 columns of one batch item's output; wave w owns the row blocks of half
-// w & 1 and the tile rows 2 (w >> 1), + 1) and the optional per-tile (sum, M2) statistics, which
-// corr_enc_norm_finalize merges unchanged.
+// The arithmetic is corr_conv.hip's: an implicit GEMM on the 16x16x32 bf16 MFMA with the build's
+// exact three-piece split (x = hi + mid + lo, six products per fp32 product in the family's
+// order (corr_bf16x6.h), two accumulators joined by split_sum), and so are the workgroup's shape
+// (4 waves, one tile of 4 rows x 16 columns of one batch item's output; wave w owns the row blocks
+// of half w & 1 and the tile rows 2 (w >> 1), + 1) and the optional per-tile (sum, M2) statistics,
+// which corr_enc_norm_finalize merges unchanged.
 //
 // Stem.  K is tap-major: tap = 7 ky + kx ascending, the cin <= 16 channels of a tap padded to 16,
 // so one 32-wide K step is two taps and the 49 taps are 25 steps (the 50th tap's weights are
@@ -29,19 +29,13 @@
 //
 // Every load is unconditional, from an address clamped into the same map; a zero is applied to
 // the loaded value afterwards.  No atomics, no scratch, nothing allocated.
-#include "corr_build_common.h"
+#include "corr_bf16x6.h"
 #include "corr_common.h"
 
 namespace corr {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kTW = 16, kTH = 4;   // pixel tile (columns x rows), corr_conv.hip's
-constexpr int kNT = 256;           // threads
-constexpr int kPad = 64;           // the packs pad the rows to a multiple of this
+constexpr int kTW = kConvTW, kTH = kConvTH, kNT = kConvNT, kPad = kConvPad;  // the family's tile (corr_bf16x6.h)
 constexpr int kStemT = 2;          // 16-row blocks per wave: 64 output rows per workgroup
 constexpr int kStemK = 7, kStemTaps = 49, kStemSteps = 25, kStemMaxCin = 16;
 constexpr int kStemPW = kTW * 2 + kStemK - 2;   // staged positions per row: 37
@@ -53,21 +47,6 @@ constexpr int kStemNLD = (kStemWords + kNT - 1) / kNT;  // staging passes per th
 constexpr int kPwT = 1;            // 32 output rows per workgroup
 constexpr int kPwXS = 16 + 4;      // words per LDS position: 16 channel pairs + pad (16-B rows)
 
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                  0, 0, 0);
-}
-
-// The six products of one K step in corr_conv.hip's order.
-__device__ __forceinline__ void six(const u32x4 (&wa)[3], const u32x4 (&xb)[3], f32x4 &acc, f32x4 &acs) {
-    acs = mfma_bf16(wa[2], xb[0], acs);
-    acs = mfma_bf16(wa[0], xb[2], acs);
-    acs = mfma_bf16(wa[1], xb[1], acs);
-    acs = mfma_bf16(wa[1], xb[0], acs);
-    acs = mfma_bf16(wa[0], xb[1], acs);
-    acc = mfma_bf16(wa[0], xb[0], acc);
-}
-
 struct FrontArgs {
     const float *in;
     const float *bias;   // [cout], or null for no bias
@@ -78,10 +57,16 @@ struct FrontArgs {
 };
 
 // C[row = 4 (lane >> 4) + r][col = lane & 15] of row block t, tile row j0 + c: + bias, store, and
-// (STATS) the tile's (sum, M2 about its own mean) per output row, corr_conv.hip's merge: a
-// butterfly over the 16 lanes of a row group per wave, the two halves of the tile (waves w and
-// w + 2) met in LDS and merged by thread `row`, upper half first (Chan et al.).  Every lane stays
-// to the end; a pixel past Ho / Wo is neither stored nor counted.
+// (STATS) the tile's (sum, M2 about its own mean) per output row: a butterfly over the 16 lanes of
+// a row group per wave (every lane ends with the same bits: each level adds the same two values in
+// either order), the squared deviations from that half's mean likewise; the two halves of the tile
+// (waves w and w + 2) meet in LDS and thread `row` merges them, upper half first (Chan et al.).
+// Every lane stays to the end (the reductions and the barrier need all of them); a pixel past Ho /
+// Wo is neither stored nor counted.
+// This is the statistics epilogue's one description; conv_kernel's STATS branch (corr_conv.hip) is
+// a copy of it for T = 1 that writes a channel window.  The two stay separate because either one
+// compiled from a shared function came out as different machine code; a change to
+// one is a change to both, and enc_finalize_kernel reads what both write.
 template <int T, bool STATS>
 __device__ __forceinline__ void front_epilogue(const FrontArgs &g, const f32x4 (&acc)[T][2], const f32x4 (&acs)[T][2],
                                                int b, int tl, int y0, int x0, float *red) {
@@ -162,9 +147,7 @@ __global__ __launch_bounds__(64) void stem_pack_kernel(const float *__restrict__
         split3(live && ca < cin ? a : 0.f, live && cb < cin ? b : 0.f, h[j], m[j], lo[j]);
     }
     u32x4 *dst = frag + (((size_t)ob * kStemSteps + s) * 3) * 64 + lane;
-    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-    dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-    dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    store_pieces(dst, h, m, lo);
 }
 
 constexpr int stem_tap_offset(int tap) {  // the window offset of a tap (the zero 50th tap reads the 49th's)
@@ -274,9 +257,7 @@ __global__ __launch_bounds__(64) void pw_pack_kernel(const float *__restrict__ w
 #pragma unroll
     for (int j = 0; j < 4; ++j) split3(live ? src[2 * j] : 0.f, live ? src[2 * j + 1] : 0.f, h[j], m[j], lo[j]);
     u32x4 *dst = frag + (((size_t)ob * (cin / 32) + ch) * 3) * 64 + lane;
-    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-    dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-    dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    store_pieces(dst, h, m, lo);
 }
 
 template <int S, bool STATS>

@@ -8,8 +8,8 @@
 //   head:  delta[b][o][y][x] = bias[o] + sum_tap (sum_c w[o][c][tap] hidden[b][off + c][y + ky - 1][x + kx - 1])
 //          coords_out = coords_in + delta;  flow_out = coords_out - coords0   (optional)
 //
-// The arithmetic is corr_conv.hip's: v_mfma_f32_16x16x32_bf16 with the build's exact three-piece
-// split (x = hi + mid + lo, six products per fp32 product in corr_conv.hip's order, two accumulators
+// The arithmetic is corr_conv.hip's: the 16x16x32 bf16 MFMA with the build's exact three-piece split
+// (x = hi + mid + lo, six products per fp32 product in the family's order (corr_bf16x6.h), two accumulators
 // joined by split_sum), every following fp32 operation rounded once.
 //
 // Encoder.  K = 98 is tap-major, tap = 7 ky + kx ascending with the two channels of a tap adjacent
@@ -33,19 +33,13 @@
 // Every load is unconditional, from an address clamped into the same map; a zero is applied to
 // the loaded value (or the product) afterwards.  No atomics, no scratch, nothing allocated.
 // Non-finite inputs are not parity-checked (corr_conv.hip's note applies).
-#include "corr_build_common.h"
+#include "corr_bf16x6.h"
 #include "corr_common.h"
 
 namespace corr {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kTW = 16, kTH = 4;   // the encoder's pixel tile (columns x rows), corr_conv.hip's
-constexpr int kNT = 256;           // threads
-constexpr int kPad = 64;           // the pack pads the rows to a multiple of this
+constexpr int kTW = kConvTW, kTH = kConvTH, kNT = kConvNT, kPad = kConvPad;  // the family's tile (corr_bf16x6.h)
 constexpr int kFeT = 2;            // 16-row blocks per wave: 64 output rows per workgroup
 constexpr int kFeK = 7, kFeTaps = 49, kFeSteps = 4, kFeStepTaps = 16;
 constexpr int kFePW = kTW + kFeK - 1;   // staged positions per row: 22
@@ -57,21 +51,6 @@ constexpr int kFhC = 256, kFhKS = kFhC / 32, kFhTaps = 9;
 constexpr int kFhTW = 14, kFhTH = 2;   // output tile; with its halo kFhTH + 2 rows of 16 pixels
 constexpr int kFhNB = kFhTH + 2;       // 16-pixel blocks (halo rows) per workgroup
 static_assert(2 * kFhTH * kFhTW <= kNT, "one thread per output value");
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                  0, 0, 0);
-}
-
-// The six products of one K step in corr_conv.hip's order.
-__device__ __forceinline__ void six(const u32x4 (&wa)[3], const u32x4 (&xb)[3], f32x4 &acc, f32x4 &acs) {
-    acs = mfma_bf16(wa[2], xb[0], acs);
-    acs = mfma_bf16(wa[0], xb[2], acs);
-    acs = mfma_bf16(wa[1], xb[1], acs);
-    acs = mfma_bf16(wa[1], xb[0], acs);
-    acs = mfma_bf16(wa[0], xb[1], acs);
-    acc = mfma_bf16(wa[0], xb[0], acc);
-}
 
 // ---------------------------------------------------------------------------------------------
 // encoder: 7x7, 2 -> cout
@@ -94,9 +73,7 @@ __global__ __launch_bounds__(64) void flow_enc_pack_kernel(const float *__restri
         split3(live ? a : 0.f, live ? b : 0.f, h[j], m[j], lo[j]);
     }
     u32x4 *dst = frag + (((size_t)ob * kFeSteps + s) * 3) * 64 + lane;
-    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-    dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-    dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    store_pieces(dst, h, m, lo);
 }
 
 struct FlowEncArgs {
@@ -214,9 +191,7 @@ __global__ __launch_bounds__(64) void flow_head_pack_kernel(const float *__restr
         split3(live ? a : 0.f, live ? b : 0.f, h[j], m[j], lo[j]);
     }
     u32x4 *dst = frag + (((size_t)o * kFhKS + ks) * 3) * 64 + lane;
-    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-    dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-    dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    store_pieces(dst, h, m, lo);
 }
 
 struct FlowHeadArgs {

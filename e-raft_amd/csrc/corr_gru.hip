@@ -13,9 +13,9 @@
 // Both are the implicit GEMM
 //   out[o][pixel] = sum_chunk sum_tap sum_{c in chunk} W[o][c][tap] * in[c][pixel + (tap - 2) step]
 // with K = 5 C in steps of 32 channels (channel chunk outer, tap inner: a fixed order), on
-// v_mfma_f32_16x16x32_bf16 with the build's exact three-piece split (x = hi + mid + lo, six
-// products per fp32 product in lookup_conv_kernel's order, two accumulators joined by split_sum:
-// no narrower than fp32, no scales).
+// the 16x16x32 bf16 MFMA with the build's exact three-piece split (x = hi + mid + lo, six
+// products per fp32 product in the family's order, corr_bf16x6.h, two accumulators joined by
+// split_sum: no narrower than fp32, no scales).
 //
 // Workgroup = 4 waves = 64 output rows x one tile of 4 rows x 16 columns of one batch item's
 // map; wave w owns rows 32 (w & 1) .. + 32 and tile rows 2 (w >> 1), + 1 (two 16x16 output tiles
@@ -33,15 +33,12 @@
 // pieces of the weights); finite inputs give finite outputs.
 #include <cmath>
 
-#include "corr_build_common.h"
+#include "corr_bf16x6.h"
+#include "corr_build_common.h"  // align256
 #include "corr_common.h"
 
 namespace corr {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kGruH = 128;                  // hidden channels
 constexpr int kGruTW = 16, kGruTH = 4;      // pixel tile (columns x rows)
@@ -52,11 +49,6 @@ constexpr int kGruTaps = 5;
 constexpr int kGruWaves = 2;                // waves per SIMD the kernel is compiled for (<= 256 registers)
 constexpr int kGruAhead = 4;                // K steps the weight fragments run ahead (< kGruTaps)
 constexpr int kGruBlocks = 3 * kGruH / 16;  // 16-row blocks of the pack: z, r, q
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                  0, 0, 0);
-}
 
 template <int DIR>
 struct GruTile {
@@ -86,9 +78,7 @@ __global__ __launch_bounds__(64) void gru_pack_kernel(const float *__restrict__ 
         for (int j = 0; j < 4; ++j)
             split3(src[(2 * j) * kGruTaps + t], src[(2 * j + 1) * kGruTaps + t], h[j], m[j], lo[j]);
         u32x4 *dst = frag + ((((size_t)ob * NC + ch) * kGruTaps + t) * 3) * 64 + lane;
-        dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-        dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-        dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        store_pieces(dst, h, m, lo);
     }
 }
 
@@ -194,18 +184,9 @@ __global__ __launch_bounds__(kGruNT, kGruWaves) void gru_kernel(GruArgs g) {
                 for (int p = 0; p < 3; ++p)
                     xb[c][p] = *reinterpret_cast<const u32x4 *>(&xs[p][(j0 + c) * T::PW + fr + tap * T::TSTEP][fk]);
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const u32x4 wh = wa[tap][t][0], wm = wa[tap][t][1], wl = wa[tap][t][2];
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    acs[t][c] = mfma_bf16(wl, xb[c][0], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wh, xb[c][2], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wm, xb[c][1], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wm, xb[c][0], acs[t][c]);
-                    acs[t][c] = mfma_bf16(wh, xb[c][1], acs[t][c]);
-                    acc[t][c] = mfma_bf16(wh, xb[c][0], acc[t][c]);
-                }
-            }
+                for (int c = 0; c < 2; ++c) six(wa[tap][t], xb[c], acc[t][c], acs[t][c]);
         }
         __syncthreads();
     };

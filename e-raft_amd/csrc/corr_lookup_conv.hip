@@ -3,19 +3,17 @@
 // and the weight packs both read.
 #include <algorithm>
 
-#include "corr_build_common.h"
+#include "corr_bf16x6.h"
 #include "corr_common.h"
 #include "corr_lookup_block.h"
 
 namespace corr {
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // Lookup fused with the consumer's 1x1 convolution (BasicMotionEncoder.convc1, update.py:68,75:
 // cor = relu(convc1(corr)), L*K = 324 -> 256 channels), on the bf16 MFMA with the build's exact
-// three-piece split (x = hi + mid + lo, six products per fp32 product, smallest first: no
-// narrower than fp32, no scales).  A workgroup owns 32 queries: two groups of 5 waves look them
+// three-piece split (x = hi + mid + lo, six products per fp32 product in the family's order,
+// corr_bf16x6.h: no narrower than fp32, no scales).  A workgroup owns 32 queries: two groups of 5 waves look them
 // up, two levels at a time (lookup_block, bit-identical values), into an LDS tile ct[L*K][32];
 // the tile is split into bf16 pieces [piece][q][k] (aliasing the lookup staging); 8 waves then
 // multiply by the pre-split weight (corr_lookup_conv_weights: W's pieces in the 16x16x32 MFMA
@@ -25,13 +23,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kLcQB = 32, kLcO = 256, kLcKC = 11, kLcKP = 32 * kLcKC /* 352 >= 4*81 */, kLcXS = kLcKP / 2 + 4;
 constexpr int kLcGT = lookup_threads(9, kLcQB), kLcNT = 2 * kLcGT;
 constexpr size_t kLcFwdU = (size_t)(kLcO / 16) * kLcKC * 3 * 64;  // u32x4 of the forward W pack
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                  0, 0, 0);
-}
 
 // weight [O][C] fp32 -> W's pieces [O/16][kLcKC][hi, mid, lo][64 lanes]: lane = 16 kg + r holds
 // W[16 ob + r][32 kc + 8 kg + j], j < 8 (zero past C).  One block of 64 lanes per (ob, kc).
@@ -46,9 +37,7 @@ __global__ __launch_bounds__(64) void lookup_conv_weights_kernel(const float *__
 #pragma unroll
     for (int j = 0; j < 4; ++j) split3(v[2 * j], v[2 * j + 1], h[j], m[j], lo[j]);
     u32x4 *dst = frag + (((size_t)ob * kLcKC + kc) * 3) * 64 + lane;
-    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-    dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-    dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    store_pieces(dst, h, m, lo);
 }
 
 struct LcSmem {
@@ -125,18 +114,9 @@ __global__ __launch_bounds__(kLcNT) void lookup_conv_kernel(ConstLevelPtrs pyr, 
             for (int p = 0; p < 3; ++p)
                 xb[c][p] = *reinterpret_cast<const u32x4 *>(&sm.u.x[p][16 * c + fr][16 * kc + fk]);
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const u32x4 wh = wa[cur][t][0], wm = wa[cur][t][1], wl = wa[cur][t][2];
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                acs[t][c] = mfma_bf16(wl, xb[c][0], acs[t][c]);
-                acs[t][c] = mfma_bf16(wh, xb[c][2], acs[t][c]);
-                acs[t][c] = mfma_bf16(wm, xb[c][1], acs[t][c]);
-                acs[t][c] = mfma_bf16(wm, xb[c][0], acs[t][c]);
-                acs[t][c] = mfma_bf16(wh, xb[c][1], acs[t][c]);
-                acc[t][c] = mfma_bf16(wh, xb[c][0], acc[t][c]);
-            }
-        }
+            for (int c = 0; c < 2; ++c) six(wa[cur][t], xb[c], acc[t][c], acs[t][c]);
     }
     // ---- epilogue: C[row = o][col = q] = acc[4 (lane >> 4) + r][lane & 15] ----
 #pragma unroll
@@ -199,9 +179,7 @@ __global__ __launch_bounds__(64) void lookup_conv_wt_kernel(const float *__restr
 #pragma unroll
     for (int j = 0; j < 4; ++j) split3(v[2 * j], v[2 * j + 1], h[j], m[j], lo[j]);
     u32x4 *dst = wt + (((size_t)l * kCbCT + ct) * kCbKS + ks) * 3 * 64 + lane;
-    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-    dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-    dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    store_pieces(dst, h, m, lo);
 }
 
 struct CbArgs {

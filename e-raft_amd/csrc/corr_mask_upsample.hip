@@ -6,10 +6,10 @@
 //   p = softmax over the 9 taps k (max-subtracted, tap order k = 0..8, as corr_convex_upsample)
 //   out[n][ch][8y + i][8x + j] = sum_k p[k] * 8 flow[n][ch][y + k/3 - 1][x + k%3 - 1]   (0 outside the map)
 //
-// The logits are the implicit GEMM [576 x 256] x [256 x pixels] on v_mfma_f32_16x16x32_bf16 with
+// The logits are the implicit GEMM [576 x 256] x [256 x pixels] on the 16x16x32 bf16 MFMA with
 // the build's exact three-piece split (x = hi + mid + lo, six products per fp32 product in
-// corr_conv.hip's order, two accumulators joined by split_sum: no narrower than fp32, no scales),
-// K in ascending steps of 32 channels.
+// the family's order (corr_bf16x6.h), two accumulators joined by split_sum: no narrower than fp32,
+// no scales), K in ascending steps of 32 channels.
 //
 // Tap ownership: the 576 rows are 9 taps x 64 sub-pixels, so a wave that owns the nine 16-row
 // blocks 64k + 16q .. + 15 (k = 0..8) of one sub-pixel range q holds, lane by lane, all nine
@@ -31,15 +31,11 @@
 // no workspace.
 //
 // Non-finite inputs are not parity-checked (corr_conv.hip's note applies).
-#include "corr_build_common.h"
+#include "corr_bf16x6.h"
 #include "corr_common.h"
 
 namespace corr {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kMuK = 256;                 // input channels
 constexpr int kMuTaps = 9;
@@ -57,11 +53,6 @@ constexpr int kMuNLD = (kMuK / 2) * kMuPX / kMuNT;  // staging passes per thread
 static_assert(kMuTaps % kMuRing == 0, "ring slots are compile-time");
 static_assert(kMuNT % kMuPX == 0 && (kMuK / 2) % (kMuNT / kMuPX) == 0, "a thread stages one pixel");
 
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                  0, 0, 0);
-}
-
 // w [576][256] fp32 -> pieces [4 q][8 K steps][9 taps][hi, mid, lo][64 lanes] in the 16x16x32
 // A-fragment order: lane = 16 kg + r holds W[64 tap + 16 q + r][32 step + 8 kg + j], j < 8.  One
 // block per (step, 9 q + tap).
@@ -72,9 +63,7 @@ __global__ __launch_bounds__(64) void mask_pack_kernel(const float *__restrict__
 #pragma unroll
     for (int j = 0; j < 4; ++j) split3(src[2 * j], src[2 * j + 1], h[j], m[j], lo[j]);
     u32x4 *dst = frag + ((size_t)(q * kMuKS + ks) * kMuTaps + k) * 3 * 64 + lane;
-    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
-    dst[64] = u32x4{m[0], m[1], m[2], m[3]};
-    dst[128] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    store_pieces(dst, h, m, lo);
 }
 
 struct MaskUpArgs {
@@ -152,16 +141,8 @@ __global__ __launch_bounds__(kMuNT, kMuWaves) void mask_upsample_kernel(MaskUpAr
 #pragma unroll
         for (int k = 0; k < kMuTaps; ++k) {
             load_a(wa[(k + kMuAhead) % kMuRing], ks * kMuTaps + k + kMuAhead);
-            const u32x4 wh = wa[k % kMuRing][0], wm = wa[k % kMuRing][1], wl = wa[k % kMuRing][2];
 #pragma unroll
-            for (int p = 0; p < kMuNP; ++p) {
-                acs[k][p] = mfma_bf16(wl, xb[p][0], acs[k][p]);
-                acs[k][p] = mfma_bf16(wh, xb[p][2], acs[k][p]);
-                acs[k][p] = mfma_bf16(wm, xb[p][1], acs[k][p]);
-                acs[k][p] = mfma_bf16(wm, xb[p][0], acs[k][p]);
-                acs[k][p] = mfma_bf16(wh, xb[p][1], acs[k][p]);
-                acc[k][p] = mfma_bf16(wh, xb[p][0], acc[k][p]);
-            }
+            for (int p = 0; p < kMuNP; ++p) six(wa[k % kMuRing], xb[p], acc[k][p], acs[k][p]);
         }
     }
 

@@ -249,6 +249,59 @@ def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+# ---- arguments that the bf16x6 convolution wrappers share ----
+def _new_pack(nbytes, device):
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+
+
+def _pack_weights(w, size_fn, pack_fn, args, what):
+    """A new pack of the contiguous fp32 weight `w` (or a dict name -> weight, in the entry point's
+    order): lib.size_fn(*args) bytes (0: CORR_EUNSUPPORTED, `what` tells the sizes), filled by
+    lib.pack_fn(weights..., *args, pack, stream)."""
+    ws = w if isinstance(w, dict) else {"w": w}
+    first = next(iter(ws.values()))
+    lib = load()
+    n = getattr(lib, size_fn)(*args)
+    if n == 0:
+        raise CorrError(CORR_EUNSUPPORTED, f"{size_fn}: unsupported {what}")
+    ptrs = [_dev(t, name) for name, t in ws.items()]
+    packed = _new_pack(n, first.device)
+    with torch.cuda.device(first.device):
+        _check(getattr(lib, pack_fn)(*ptrs, *args, packed.data_ptr(), _stream(first)))
+    return packed
+
+
+def _pack_arg(packed, need, device, what):
+    """The pointer of a pack, which must hold the `need` bytes that `what` reads, on `device`."""
+    pk = _dev(packed, "packed")
+    if packed.numel() * 4 < need or packed.device != device:
+        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, {what} needs "
+                         f"{need} on {device}")
+    return pk
+
+
+def _bias_arg(bias, n, device, optional=True):
+    """The pointer of a bias of n values on `device`; None for no bias where the kernel takes that."""
+    if bias is None and optional:
+        return None
+    bp = _dev(bias, "bias")
+    if bias.numel() != n or bias.device != device:
+        raise ValueError(f"bias must hold {'cout = ' if optional else ''}{n} values on {device} "
+                         f"(got {tuple(bias.shape)})")
+    return bp
+
+
+def _window_arg(t, name, B, H, W, offset, n, device):
+    """The pointer of `t`, which must be a [B, *, H, W] map on `device` with channels offset ..
+    offset + n - 1."""
+    tp = _dev(t, name)
+    if (t.dim() != 4 or t.shape[0] != B or tuple(t.shape[2:]) != (H, W) or t.device != device
+            or offset < 0 or offset + n > t.shape[1]):
+        raise ValueError(f"{name} {tuple(t.shape)} does not hold channels {offset} .. {offset + n - 1} "
+                         f"of a [{B}, *, {H}, {W}] map on {device}")
+    return tp
+
+
 def _nq(t):
     """Query pixels per batch item of a [B, C, rows, W] (or [B, C, NQ]) tensor."""
     n = 1
@@ -541,7 +594,7 @@ def lookup_conv_weights(weight):
     """corr_lookup_conv_weights: convc1.weight [256, C(, 1, 1)] -> the packed split (an opaque buffer)."""
     w = weight.detach().reshape(weight.shape[0], -1).contiguous().float()
     lib = load()
-    packed = torch.empty((lib.corr_lookup_conv_weights_bytes() + 3) // 4, dtype=torch.float32, device=w.device)
+    packed = _new_pack(lib.corr_lookup_conv_weights_bytes(), w.device)
     with torch.cuda.device(w.device):
         _check(lib.corr_lookup_conv_weights(_dev(w, "weight"), w.shape[0], w.shape[1], packed.data_ptr(),
                                             _stream(w)))
@@ -671,15 +724,8 @@ def gru_pack_weights(wz, wr, wq):
         if w.dim() != 4 or w.shape[0] != hidden or w.shape[1] != C or w.shape[2] * w.shape[3] != 5:
             raise ValueError(f"GRU gate weights must be [hidden, C, 1, 5] or [hidden, C, 5, 1] "
                              f"(got {[tuple(v.shape) for v in ws]})")
-    lib = load()
-    n = lib.corr_gru_weights_bytes(hidden, C - hidden)
-    if n == 0:
-        raise CorrError(CORR_EUNSUPPORTED, f"corr_gru_weights_bytes: unsupported hidden = {hidden}, C = {C}")
-    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=ws[0].device)
-    with torch.cuda.device(ws[0].device):
-        _check(lib.corr_gru_pack_weights(_dev(ws[0], "wz"), _dev(ws[1], "wr"), _dev(ws[2], "wq"), hidden, C - hidden,
-                                         packed.data_ptr(), _stream(ws[0])))
-    return packed
+    return _pack_weights(dict(zip(("wz", "wr", "wq"), ws)), "corr_gru_weights_bytes", "corr_gru_pack_weights",
+                         (hidden, C - hidden), f"hidden = {hidden}, C = {C}")
 
 
 def gru_half_step(h, x, direction, packed, bz, br, bq, workspace=None):
@@ -717,15 +763,8 @@ def conv_pack_weights(weights):
     ws = [w.detach().float() for w in ws]
     w = (ws[0] if len(ws) == 1 else torch.cat(ws, dim=0)).contiguous()
     cout, cin = w.shape[0], w.shape[1]
-    lib = load()
-    n = lib.corr_conv_weights_bytes(cout, cin)
-    if n == 0:
-        raise CorrError(CORR_EUNSUPPORTED, f"corr_conv_weights_bytes: unsupported cout = {cout}, cin = {cin}")
-    wp = _dev(w, "w")
-    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(lib.corr_conv_pack_weights(wp, cout, cin, packed.data_ptr(), _stream(w)))
-    return packed
+    return _pack_weights(w, "corr_conv_weights_bytes", "corr_conv_pack_weights", (cout, cin),
+                         f"cout = {cout}, cin = {cin}")
 
 
 def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0):
@@ -748,24 +787,13 @@ def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0):
     need = lib.corr_conv_weights_bytes(cout, ca + cb)
     if need == 0:
         raise CorrError(CORR_EUNSUPPORTED, f"corr_conv_forward: unsupported cout = {cout}, ca = {ca}, cb = {cb}")
-    pk = _dev(packed, "packed")
-    if packed.numel() * 4 < need or packed.device != in_a.device:
-        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
-                         f"{need} on {in_a.device}")
-    biasp = None
-    if bias is not None:
-        biasp = _dev(bias, "bias")
-        if bias.numel() != cout or bias.device != in_a.device:
-            raise ValueError(f"bias must hold cout = {cout} values on {in_a.device} (got {tuple(bias.shape)})")
+    pk = _pack_arg(packed, need, in_a.device, "the convolution")
+    biasp = _bias_arg(bias, cout, in_a.device)
     if out is None:
         if out_offset != 0:
             raise ValueError("out_offset needs an out tensor")
         out = torch.empty((B, cout, H, W), dtype=torch.float32, device=in_a.device)
-    op = _dev(out, "out")
-    if (out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (H, W) or out.device != in_a.device
-            or out_offset < 0 or out_offset + cout > out.shape[1]):
-        raise ValueError(f"out {tuple(out.shape)} does not hold channels {out_offset} .. {out_offset + cout - 1} "
-                         f"of a [{B}, *, {H}, {W}] map on {in_a.device}")
+    op = _window_arg(out, "out", B, H, W, out_offset, cout, in_a.device)
     with torch.cuda.device(in_a.device):
         _check(lib.corr_conv_forward(ap, ca, bp, cb, B, H, W, pk, biasp, cout, int(bool(relu)), op, out.shape[1],
                                      out_offset, _stream(in_a)))
@@ -779,13 +807,8 @@ def mask_upsample_pack_weights(w):
         raise TypeError("w must be a torch.Tensor")
     if tuple(w.shape) not in ((576, 256, 1, 1), (576, 256)):
         raise ValueError(f"w must be [576, 256, 1, 1] (got {tuple(w.shape)})")
-    w = w.detach().float().contiguous()
-    wp = _dev(w, "w")
-    lib = load()
-    packed = torch.empty((lib.corr_mask_upsample_weights_bytes() + 3) // 4, dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(lib.corr_mask_upsample_pack_weights(wp, packed.data_ptr(), _stream(w)))
-    return packed
+    return _pack_weights(w.detach().float().contiguous(), "corr_mask_upsample_weights_bytes",
+                         "corr_mask_upsample_pack_weights", (), "")
 
 
 def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=None):
@@ -807,13 +830,8 @@ def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=
                          f"{flow.device})")
     lib = load()
     need = lib.corr_mask_upsample_weights_bytes()
-    pk = _dev(packed, "packed")
-    if packed.numel() * 4 < need or packed.device != hidden.device:
-        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the mask head needs "
-                         f"{need} on {hidden.device}")
-    bp = _dev(bias, "bias")
-    if bias.numel() != 576 or bias.device != hidden.device:
-        raise ValueError(f"bias must hold 576 values on {hidden.device} (got {tuple(bias.shape)})")
+    pk = _pack_arg(packed, need, hidden.device, "the mask head")
+    bp = _bias_arg(bias, 576, hidden.device, optional=False)
     if out is None:
         out = torch.empty((B, 2, 8 * H, 8 * W), dtype=torch.float32, device=hidden.device)
     op = _dev(out, "out")
@@ -832,17 +850,8 @@ def flow_enc_pack_weights(w):
         raise TypeError("w must be a torch.Tensor")
     if w.dim() != 4 or tuple(w.shape[1:]) != (2, 7, 7):
         raise ValueError(f"w must be [cout, 2, 7, 7] (got {tuple(w.shape)})")
-    w = w.detach().float().contiguous()
-    cout = w.shape[0]
-    lib = load()
-    n = lib.corr_flow_enc_weights_bytes(cout)
-    if n == 0:
-        raise CorrError(CORR_EUNSUPPORTED, f"corr_flow_enc_weights_bytes: unsupported cout = {cout}")
-    wp = _dev(w, "w")
-    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(lib.corr_flow_enc_pack_weights(wp, cout, packed.data_ptr(), _stream(w)))
-    return packed
+    return _pack_weights(w.detach().float().contiguous(), "corr_flow_enc_weights_bytes",
+                         "corr_flow_enc_pack_weights", (w.shape[0],), f"cout = {w.shape[0]}")
 
 
 def flow_enc_forward(flow, packed, bias, cout, relu, out=None, out_offset=0, flow_copy=None, copy_offset=0):
@@ -859,32 +868,16 @@ def flow_enc_forward(flow, packed, bias, cout, relu, out=None, out_offset=0, flo
     need = lib.corr_flow_enc_weights_bytes(cout)
     if need == 0:
         raise CorrError(CORR_EUNSUPPORTED, f"corr_flow_enc_forward: unsupported cout = {cout}")
-    pk = _dev(packed, "packed")
-    if packed.numel() * 4 < need or packed.device != flow.device:
-        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
-                         f"{need} on {flow.device}")
-    biasp = None
-    if bias is not None:
-        biasp = _dev(bias, "bias")
-        if bias.numel() != cout or bias.device != flow.device:
-            raise ValueError(f"bias must hold cout = {cout} values on {flow.device} (got {tuple(bias.shape)})")
+    pk = _pack_arg(packed, need, flow.device, "the convolution")
+    biasp = _bias_arg(bias, cout, flow.device)
     if out is None:
         if out_offset != 0:
             raise ValueError("out_offset needs an out tensor")
         out = torch.empty((B, cout, H, W), dtype=torch.float32, device=flow.device)
-    op = _dev(out, "out")
-    if (out.dim() != 4 or out.shape[0] != B or tuple(out.shape[2:]) != (H, W) or out.device != flow.device
-            or out_offset < 0 or out_offset + cout > out.shape[1]):
-        raise ValueError(f"out {tuple(out.shape)} does not hold channels {out_offset} .. {out_offset + cout - 1} "
-                         f"of a [{B}, *, {H}, {W}] map on {flow.device}")
+    op = _window_arg(out, "out", B, H, W, out_offset, cout, flow.device)
     cp, cc = None, 0
     if flow_copy is not None:
-        cp = _dev(flow_copy, "flow_copy")
-        if (flow_copy.dim() != 4 or flow_copy.shape[0] != B or tuple(flow_copy.shape[2:]) != (H, W)
-                or flow_copy.device != flow.device or copy_offset < 0 or copy_offset + 2 > flow_copy.shape[1]):
-            raise ValueError(f"flow_copy {tuple(flow_copy.shape)} does not hold channels {copy_offset}, "
-                             f"{copy_offset + 1} of a [{B}, *, {H}, {W}] map on {flow.device}")
-        cc = flow_copy.shape[1]
+        cp, cc = _window_arg(flow_copy, "flow_copy", B, H, W, copy_offset, 2, flow.device), flow_copy.shape[1]
     elif copy_offset != 0:
         raise ValueError("copy_offset needs a flow_copy tensor")
     with torch.cuda.device(flow.device):
@@ -900,13 +893,8 @@ def flow_head_pack_weights(w):
         raise TypeError("w must be a torch.Tensor")
     if tuple(w.shape) != (2, 256, 3, 3):
         raise ValueError(f"w must be [2, 256, 3, 3] (got {tuple(w.shape)})")
-    w = w.detach().float().contiguous()
-    wp = _dev(w, "w")
-    lib = load()
-    packed = torch.empty((lib.corr_flow_head_weights_bytes() + 3) // 4, dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(lib.corr_flow_head_pack_weights(wp, packed.data_ptr(), _stream(w)))
-    return packed
+    return _pack_weights(w.detach().float().contiguous(), "corr_flow_head_weights_bytes",
+                         "corr_flow_head_pack_weights", (), "")
 
 
 def flow_head_forward(hidden, hidden_offset, packed, bias, coords_in=None, coords0=None, delta=None,
@@ -926,13 +914,8 @@ def flow_head_forward(hidden, hidden_offset, packed, bias, coords_in=None, coord
                          f"{hidden_offset + 255}")
     lib = load()
     need = lib.corr_flow_head_weights_bytes()
-    pk = _dev(packed, "packed")
-    if packed.numel() * 4 < need or packed.device != hidden.device:
-        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the flow head needs "
-                         f"{need} on {hidden.device}")
-    bp = _dev(bias, "bias")
-    if bias.numel() != 2 or bias.device != hidden.device:
-        raise ValueError(f"bias must hold 2 values on {hidden.device} (got {tuple(bias.shape)})")
+    pk = _pack_arg(packed, need, hidden.device, "the flow head")
+    bp = _bias_arg(bias, 2, hidden.device, optional=False)
     if coords0 is not None and coords_in is None:
         raise ValueError("coords0 needs coords_in")
 
@@ -984,15 +967,8 @@ def enc_conv_forward(x, packed, bias, cout, stride=1, in_scale=None, in_shift=No
     if need == 0 or stride not in (1, 2):
         raise CorrError(CORR_EUNSUPPORTED,
                         f"corr_enc_conv_forward: unsupported cout = {cout}, cin = {cin}, stride = {stride}")
-    pk = _dev(packed, "packed")
-    if packed.numel() * 4 < need or packed.device != x.device:
-        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
-                         f"{need} on {x.device}")
-    biasp = None
-    if bias is not None:
-        biasp = _dev(bias, "bias")
-        if bias.numel() != cout or bias.device != x.device:
-            raise ValueError(f"bias must hold cout = {cout} values on {x.device} (got {tuple(bias.shape)})")
+    pk = _pack_arg(packed, need, x.device, "the convolution")
+    biasp = _bias_arg(bias, cout, x.device)
     if (in_scale is None) != (in_shift is None):
         raise ValueError("in_scale and in_shift must both be given or both be None")
     sp, hp, nb = (None, None, 0) if in_scale is None else _enc_norm(in_scale, in_shift, B, cin, x.device, "in")
@@ -1048,17 +1024,9 @@ def _enc_front_pack(w, k, name):
         raise TypeError("w must be a torch.Tensor")
     if not (w.dim() == 4 and tuple(w.shape[2:]) == (k, k)) and not (k == 1 and w.dim() == 2):
         raise ValueError(f"w must be [cout, cin, {k}, {k}] (got {tuple(w.shape)})")
-    w = w.detach().float().contiguous()
     cout, cin = w.shape[0], w.shape[1]
-    wp = _dev(w, "w")
-    lib = load()
-    n = getattr(lib, f"corr_enc_{name}_weights_bytes")(cout, cin)
-    if n == 0:
-        raise CorrError(CORR_EUNSUPPORTED, f"corr_enc_{name}_weights_bytes: unsupported cout = {cout}, cin = {cin}")
-    packed = torch.empty((n + 3) // 4, dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(getattr(lib, f"corr_enc_{name}_pack_weights")(wp, cout, cin, packed.data_ptr(), _stream(w)))
-    return packed
+    return _pack_weights(w.detach().float().contiguous(), f"corr_enc_{name}_weights_bytes",
+                         f"corr_enc_{name}_pack_weights", (cout, cin), f"cout = {cout}, cin = {cin}")
 
 
 def enc_stem_pack_weights(w):
@@ -1083,15 +1051,8 @@ def _enc_front_forward(name, x, packed, bias, cout, stride, stats):
     if need == 0 or stride not in (1, 2):
         raise CorrError(CORR_EUNSUPPORTED,
                         f"corr_enc_{name}_forward: unsupported cout = {cout}, cin = {cin}, stride = {stride}")
-    pk = _dev(packed, "packed")
-    if packed.numel() * 4 < need or packed.device != x.device:
-        raise ValueError(f"packed holds {packed.numel() * 4} bytes on {packed.device}, the convolution needs "
-                         f"{need} on {x.device}")
-    biasp = None
-    if bias is not None:
-        biasp = _dev(bias, "bias")
-        if bias.numel() != cout or bias.device != x.device:
-            raise ValueError(f"bias must hold cout = {cout} values on {x.device} (got {tuple(bias.shape)})")
+    pk = _pack_arg(packed, need, x.device, "the convolution")
+    biasp = _bias_arg(bias, cout, x.device)
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     out = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x.device)
     st, nst = None, 0

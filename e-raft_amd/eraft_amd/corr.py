@@ -21,11 +21,10 @@ avg-pool backward folded into level 0 in one pass, and the two MFMA GEMMs.
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 
 from . import _lib
+from ._cache import cached
 
 
 def level_shapes(H: int, W: int, num_levels: int):
@@ -85,25 +84,9 @@ def _validate_fmaps(fmap1, fmap2, num_levels):
         raise RuntimeError(f"{H}x{W} feature maps are too small for {num_levels} pyramid levels")
 
 
-_WEIGHT_PACKS = {}  # id(weight) -> (weakref to the weight, (data_ptr, _version), pack)
-
-
 def _weight_pack(weight):
-    """convc1.weight's packed split for lookup_conv, cached per weight tensor in a module-level
-    map keyed by the tensor's id and held by a weak reference (nothing is attached to the
-    Parameter, so pickling or torch.save of the model is unaffected, and the entry goes when the
-    tensor does), together with the (data_ptr, _version) it was made from: a new tensor
-    (another model, a reloaded checkpoint) never sees another tensor's pack, and an in-place
-    update (optimizer step, load_state_dict's copy_) bumps _version and re-packs.  (A
-    WeakKeyDictionary cannot hold tensors: its key comparison calls Tensor.__eq__.)"""
-    key = (weight.data_ptr(), weight._version)
-    wid = id(weight)
-    ent = _WEIGHT_PACKS.get(wid)
-    if ent is None or ent[0]() is not weight or ent[1] != key:
-        ref = weakref.ref(weight, lambda _r, wid=wid: _WEIGHT_PACKS.pop(wid, None))
-        ent = (ref, key, _lib.lookup_conv_weights(weight))
-        _WEIGHT_PACKS[wid] = ent
-    return ent[2]
+    """convc1.weight's packed split for lookup_conv and its backward (cached: _cache.py)."""
+    return cached("lookup_conv", (weight,), "lookup_conv: convc1's pack", lambda: _lib.lookup_conv_weights(weight))
 
 
 class _State:
@@ -399,9 +382,9 @@ class CorrBlock:
             if token is None:  # the pyramid is constant; gradients reach only the weight and bias
                 token = coords.new_empty(())
             return _LookupConvFn.apply(coords, token, weight, bias, relu, self.radius, self._state)
-        cached = _weight_pack(weight)  # split once per weight version (every GRU iteration reuses it)
+        packed = _weight_pack(weight)  # split once per weight version (every GRU iteration reuses it)
         out = torch.empty((B, weight.shape[0], H, W), dtype=torch.float32, device=coords.device)
-        _lib.lookup_conv(self._state.levels, coords, self.radius, cached,
+        _lib.lookup_conv(self._state.levels, coords, self.radius, packed,
                          bias.detach().contiguous().float(), out, relu)
         return out
 

@@ -13,12 +13,11 @@ not recording.
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._cache import cached
 from .update import _conv_pack
 
 # Which pieces take the HIP kernel under the switch (each is judged on its own
@@ -30,51 +29,27 @@ USE_KERNEL = {"layer1": True, "layer2.s2": True, "layer2": True, "layer3.s2": Tr
 
 STEM_MAX_CIN = 16  # corr_enc_stem_forward's bound; a wider stem runs on torch (the stem alone)
 
-_BN_AFFINE = {}  # ids of a BatchNorm2d's tensors -> (weakrefs to them, their (data_ptr, _version)s, scale, shift)
-_FRONT_PACKS = {}  # ids of a conv's weight and bias -> (weakrefs to them, their (data_ptr, _version)s, pack, bias)
-
-
 def _bn_affine(norm):
     """(scale, shift), [C] each, of an eval-mode BatchNorm2d: scale = gamma / sqrt(running_var +
-    eps), shift = beta - running_mean * scale.  Cached like the packs: by the tensors' ids, held by
-    weak references, with the (data_ptr, _version)s they were made from, so an in-place update of
-    a parameter or a running statistic recomputes."""
-    ts = tuple(t for t in (norm.weight, norm.bias, norm.running_mean, norm.running_var) if t is not None)
-    ids = tuple(id(t) for t in ts)
-    key = tuple((t.data_ptr(), t._version) for t in ts) + (norm.eps,)
-    ent = _BN_AFFINE.get(ids)
-    if ent is None or any(r() is not t for r, t in zip(ent[0], ts)) or ent[1] != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("encoder_forward: the batch norms' scale and shift must be made before a graph "
-                               "capture (run one forward outside the capture first)")
-        drop = lambda _r, ids=ids: _BN_AFFINE.pop(ids, None)
+    eps), shift = beta - running_mean * scale (cached: _cache.py; an in-place update of a parameter
+    or a running statistic recomputes)."""
+    def make():
         scale = torch.rsqrt(norm.running_var.detach().float() + norm.eps)
         if norm.weight is not None:
             scale = norm.weight.detach().float() * scale
         shift = -norm.running_mean.detach().float() * scale
         if norm.bias is not None:
             shift = norm.bias.detach().float() + shift
-        ent = (tuple(weakref.ref(t, drop) for t in ts), key, scale.contiguous(), shift.contiguous())
-        _BN_AFFINE[ids] = ent
-    return ent[2], ent[3]
+        return scale.contiguous(), shift.contiguous()
+    ts = tuple(t for t in (norm.weight, norm.bias, norm.running_mean, norm.running_var) if t is not None)
+    return cached("bn_affine", ts, "encoder_forward: the batch norms' scale and shift", make, extra=(norm.eps,))
 
 
 def _front_pack(conv, pack):
     """(pack, bias) of the stem or a 1x1 Conv2d, made by `pack` (_lib.enc_stem_pack_weights or
-    _lib.enc_pw_pack_weights) and cached with update._conv_pack's scheme: keyed by the parameters'
-    ids, held by weak references, together with the (data_ptr, _version)s they were made from."""
-    ts = (conv.weight, conv.bias)
-    ids = tuple(id(t) for t in ts)
-    key = tuple((t.data_ptr(), t._version) for t in ts)
-    ent = _FRONT_PACKS.get(ids)
-    if ent is None or any(r() is not t for r, t in zip(ent[0], ts)) or ent[1] != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("encoder_forward: the convolution weights must be packed before a graph capture "
-                               "(run one forward outside the capture first)")
-        drop = lambda _r, ids=ids: _FRONT_PACKS.pop(ids, None)
-        ent = (tuple(weakref.ref(t, drop) for t in ts), key, pack(conv.weight), conv.bias.detach().float().contiguous())
-        _FRONT_PACKS[ids] = ent
-    return ent[2], ent[3]
+    _lib.enc_pw_pack_weights; cached: _cache.py)."""
+    return cached("front", (conv.weight, conv.bias), "encoder_forward: the convolutions' pack",
+                  lambda: (pack(conv.weight), conv.bias.detach().float().contiguous().clone()))
 
 
 def _affine(y, scale, shift):

@@ -5,33 +5,15 @@ model.SepConvGRU takes this path only when autograd is not recording.
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 
 from . import _lib
-
-_GRU_PACKS = {}  # ids of (wz, wr, wq) -> (weakrefs to them, their (data_ptr, _version)s, pack)
-
+from ._cache import cached
 
 def _gru_pack(wz, wr, wq):
-    """The packed split of one half step's three gate weights, cached with corr._weight_pack's
-    scheme: keyed by the tensors' ids, held by weak references (nothing is attached to the
-    Parameters, and the entry goes when any of them does), together with the (data_ptr,
-    _version) triple it was made from, so another module's tensors never see this pack and an
-    in-place update (optimizer step, load_state_dict's copy_) re-packs."""
-    ws = (wz, wr, wq)
-    ids = tuple(id(w) for w in ws)
-    key = tuple((w.data_ptr(), w._version) for w in ws)
-    ent = _GRU_PACKS.get(ids)
-    if ent is None or any(r() is not w for r, w in zip(ent[0], ws)) or ent[1] != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("sepconv_gru: the GRU weights must be packed before a graph capture "
-                               "(run one forward outside the capture first)")
-        drop = lambda _r, ids=ids: _GRU_PACKS.pop(ids, None)
-        ent = (tuple(weakref.ref(w, drop) for w in ws), key, _lib.gru_pack_weights(wz, wr, wq))
-        _GRU_PACKS[ids] = ent
-    return ent[2]
+    """The packed split of one half step's three gate weights (cached: _cache.py)."""
+    return cached("gru", (wz, wr, wq), "sepconv_gru: the GRU weights' pack",
+                  lambda: _lib.gru_pack_weights(wz, wr, wq))
 
 
 def half_step(module, h, x, tag):

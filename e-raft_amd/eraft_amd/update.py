@@ -9,61 +9,36 @@ model.BasicUpdateBlock takes this path only when autograd is not recording.
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._cache import cached
 
 # Which convolutions take the HIP kernel under the switch (each is judged on its
 # own against the torch ops it replaces, at DSEC and at b8).  One that is False runs on MIOpen and
 # is copied into the shared buffer.
 USE_KERNEL = {"convc2": True, "convf2": True, "conv": True, "heads": True, "convf1": True, "flow_head2": True}
 
-# (kind of pack, ids of the weights and biases) -> (weakrefs to them, their (data_ptr, _version)s, pack, bias)
-_CONV_PACKS = {}
-
-
-def _cached_pack(kind, ts, what, make):
-    """`make()`'s (pack, bias) for the parameter tensors `ts`, cached with gru._gru_pack's scheme:
-    keyed by the kind of pack and the parameters' ids, held by weak references, together with the
-    (data_ptr, _version)s they were made from, so another module's tensors never see this pack and
-    an in-place update re-packs."""
-    ids = (kind,) + tuple(id(t) for t in ts)
-    key = tuple((t.data_ptr(), t._version) for t in ts)
-    ent = _CONV_PACKS.get(ids)
-    if ent is None or any(r() is not t for r, t in zip(ent[0], ts)) or ent[1] != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"update_block: {what} must be packed before a graph capture "
-                               "(run one forward outside the capture first)")
-        drop = lambda _r, ids=ids: _CONV_PACKS.pop(ids, None)
-        pack, bias = make()
-        ent = (tuple(weakref.ref(t, drop) for t in ts), key, pack, bias)
-        _CONV_PACKS[ids] = ent
-    return ent[2], ent[3]
-
-
 def _conv_pack(convs):
-    """(pack, bias) of one launch's Conv2d modules (their weights stacked along cout)."""
+    """(pack, bias) of one launch's Conv2d modules, their weights stacked along cout (cached, as
+    the two below: _cache.py)."""
     ts = tuple(c.weight for c in convs) + tuple(c.bias for c in convs)
-    return _cached_pack("conv", ts, "the convolution weights",
-                        lambda: (_lib.conv_pack_weights([c.weight for c in convs]),
-                                 torch.cat([c.bias.detach().float() for c in convs]).contiguous()))
+    return cached("conv", ts, "update_block: the convolutions' pack",
+                  lambda: (_lib.conv_pack_weights([c.weight for c in convs]),
+                           torch.cat([c.bias.detach().float() for c in convs]).contiguous()))
 
 
 def _flow_enc_pack(conv):
     """(pack, bias) of the 7x7 flow convolution."""
-    return _cached_pack("flow_enc", (conv.weight, conv.bias), "the flow convolution's weights",
-                        lambda: (_lib.flow_enc_pack_weights(conv.weight),
-                                 conv.bias.detach().float().contiguous().clone()))
+    return cached("flow_enc", (conv.weight, conv.bias), "update_block: the flow convolution's pack",
+                  lambda: (_lib.flow_enc_pack_weights(conv.weight), conv.bias.detach().float().contiguous().clone()))
 
 
 def _flow_head_pack(conv):
     """(pack, bias) of the flow head's second convolution."""
-    return _cached_pack("flow_head", (conv.weight, conv.bias), "the flow head's weights",
-                        lambda: (_lib.flow_head_pack_weights(conv.weight),
-                                 conv.bias.detach().float().contiguous().clone()))
+    return cached("flow_head", (conv.weight, conv.bias), "update_block: the flow head's pack",
+                  lambda: (_lib.flow_head_pack_weights(conv.weight), conv.bias.detach().float().contiguous().clone()))
 
 
 def _conv(name, convs, x, out, off):

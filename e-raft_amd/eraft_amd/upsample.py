@@ -7,33 +7,16 @@ so model.ERAFT takes this path only when autograd is not recording.
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 
 from . import _lib
-
-_MASK_PACKS = {}  # ids of the weight and bias -> (weakrefs to them, their (data_ptr, _version)s, pack, bias)
-
+from ._cache import cached
 
 def _mask_pack(conv):
-    """(pack, bias) of the mask head's 1x1 Conv2d, cached with update._conv_pack's scheme: keyed by
-    the parameters' ids, held by weak references, together with the (data_ptr, _version)s they
-    were made from, so another module's tensors never see this pack and an in-place update
-    re-packs."""
-    ts = (conv.weight, conv.bias)
-    ids = tuple(id(t) for t in ts)
-    key = tuple((t.data_ptr(), t._version) for t in ts)
-    ent = _MASK_PACKS.get(ids)
-    if ent is None or any(r() is not t for r, t in zip(ent[0], ts)) or ent[1] != key:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("mask_upsample: the mask head's weights must be packed before a graph capture "
-                               "(run one forward outside the capture first)")
-        drop = lambda _r, ids=ids: _MASK_PACKS.pop(ids, None)
-        bias = conv.bias.detach().float().contiguous().clone()
-        ent = (tuple(weakref.ref(t, drop) for t in ts), key, _lib.mask_upsample_pack_weights(conv.weight), bias)
-        _MASK_PACKS[ids] = ent
-    return ent[2], ent[3]
+    """(pack, bias) of the mask head's 1x1 Conv2d (cached: _cache.py)."""
+    return cached("mask", (conv.weight, conv.bias), "mask_upsample: the mask head's pack",
+                  lambda: (_lib.mask_upsample_pack_weights(conv.weight),
+                           conv.bias.detach().float().contiguous().clone()))
 
 
 def channel_window(t):

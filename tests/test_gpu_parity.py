@@ -574,10 +574,10 @@ def test_build_bwd_bf16x6_not_narrower_than_fp32(case):
 def test_build_bwd_bf16x6_inf_matches_fp32(D, H, W):
     """Non-finite inputs of the bf16x6 backward GEMMs give the fp32 reference's results
     (include/corr_mi355x.h, corr_build_bwd_ex): the split makes every output an infinite element
-    reaches NaN (inf * 0 pieces), and the reduce / direct epilogue recompute exactly those as the
+    reaches NaN (inf * 0 pieces), and the split-K reduces recompute exactly those as the
     reference does, so +-inf land where the fp32-operand GEMMs put them and NaN (inf * 0 in the
-    fp32 sum, a NaN element) stays NaN.  Shapes: D 16 (one split, sqrt(D) a power of two: the
-    direct epilogue), D 32 (one split, the reduce kernel / dF2's tail), D 64 at 32x48 (split-K).
+    fp32 sum, a NaN element) stays NaN.  Shapes: D 16 (one split, sqrt(D) a power of two), D 32
+    (one split, the reduce kernel / dF2's tail), D 64 at 32x48 (split-K).
     Every finite output matches the fp32-operand GEMMs within 1e-6 of the scale."""
     from eraft_amd import _lib
     B = 1
