@@ -490,6 +490,28 @@ int corr_lookup_conv(const float *const *pyr, const float *coords, int B, int H,
                       fn);
 }
 
+int corr_ondemand_lookup_conv(const void *workspace, const float *coords, int B, int D, int H, int W, int levels,
+                              int radius, int flags, const void *packed_weight, const float *bias, int relu,
+                              float *out, void *stream) {
+    static const char *fn = "corr_ondemand_lookup_conv";
+    g_err[0] = 0;
+    int rc = check_ondemand(fn, B, D, H, W, levels);
+    if (rc || (rc = check_radius(fn, radius))) return rc;
+    if (flags & ~CORR_ONDEMAND_GENERAL) return fail(CORR_EINVAL, "%s: unknown flags 0x%x", fn, flags);
+    if (!workspace) return fail(CORR_EINVAL, "%s: workspace is NULL", fn);
+    if ((uintptr_t)workspace % 16) return fail(CORR_EINVAL, "%s: workspace is not 16-byte aligned", fn);
+    if ((rc = check_ptr(fn, coords, "coords"))) return rc;
+    if (radius != 4 || levels > 4)
+        return fail(CORR_EUNSUPPORTED, "%s: built for radius 4 and <= 4 levels (got %d, %d)", fn, radius, levels);
+    if ((rc = check_ptr(fn, packed_weight, "packed_weight")) || (rc = check_ptr(fn, bias, "bias")) ||
+        (rc = check_ptr(fn, out, "out")))
+        return rc;
+    if ((uintptr_t)packed_weight % 16) return fail(CORR_EINVAL, "%s: packed_weight is not 16-byte aligned", fn);
+    return hip_status(launch_ondemand_lookup_conv(workspace, coords, B, D, H, W, levels, radius, flags, packed_weight,
+                                                  bias, relu, out, (hipStream_t)stream),
+                      fn);
+}
+
 size_t corr_lookup_conv_bwd_workspace(int B, int H, int W, int levels) {
     if (B < 1 || H < 1 || W < 1 || levels < 1 || levels > 4) return 0;
     return lookup_conv_bwd_workspace(B, H * W, levels);

@@ -1,8 +1,8 @@
 // The bf16x6 family's device code: fp32 products on v_mfma_f32_16x16x32_bf16 through the exact
 // three-piece split (x = hi + mid + lo), six piece products per fp32 product.  Shared by the
 // split build and backward (the split only) and by the convolution kernels (corr_lookup_conv,
-// corr_gru, corr_conv, corr_mask_upsample, corr_enc_front, corr_flow .hip).  Internal, not part
-// of the C-ABI.
+// corr_ondemand_conv, corr_gru, corr_conv, corr_mask_upsample, corr_enc_front, corr_flow .hip).
+// Internal, not part of the C-ABI.
 #pragma once
 
 #include "corr_common.h"

@@ -194,6 +194,10 @@ hipError_t launch_ondemand_prepare(const float *f1, const float *f2, int B, int 
                                    hipStream_t s);
 hipError_t launch_ondemand_lookup(const void *ws, const float *coords, int B, int D, int H, int W, int levels,
                                   int radius, int flags, float *out, hipStream_t s);
+// The lookup fused with convc1 (corr_ondemand_conv.hip): `packed` is launch_lookup_conv_weights' pack.
+hipError_t launch_ondemand_lookup_conv(const void *ws, const float *coords, int B, int D, int H, int W, int levels,
+                                       int radius, int flags, const void *packed, const float *bias, int relu,
+                                       float *out, hipStream_t s);
 // Its backward (corr_ondemand_bwd.hip): accumulator rows and one lookup's window blocks in `bwd_ws`;
 // df1 / df2 may be null (that side is skipped).  0 bytes = sizes the backward does not accept.
 size_t ondemand_bwd_workspace_bytes(int B, int D, int H, int W, int levels, int radius);

@@ -40,7 +40,8 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_weights_bytes",
            "corr_enc_pw_pack_weights", "corr_enc_pw_forward", "corr_enc_join_affine",
            "corr_flow_enc_weights_bytes", "corr_flow_enc_pack_weights", "corr_flow_enc_forward",
-           "corr_flow_head_weights_bytes", "corr_flow_head_pack_weights", "corr_flow_head_forward")
+           "corr_flow_head_weights_bytes", "corr_flow_head_pack_weights", "corr_flow_head_forward",
+           "corr_ondemand_lookup_conv")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -148,6 +149,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_ondemand_workspace.restype = sz
     lib.corr_ondemand_prepare.argtypes = [vp, vp, i, i, i, i, i, vp, sz, vp]
     lib.corr_ondemand_lookup.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp]
+    lib.corr_ondemand_lookup_conv.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp, i, vp, vp]
     lib.corr_ondemand_bwd_workspace.argtypes = [i, i, i, i, i, i]
     lib.corr_ondemand_bwd_workspace.restype = sz
     lib.corr_ondemand_backward.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, sz, vp, vp, vp]
@@ -178,7 +180,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_flow_head_weights_bytes.argtypes, lib.corr_flow_head_weights_bytes.restype = [], sz
     lib.corr_flow_head_pack_weights.argtypes = [vp, vp, vp]
     lib.corr_flow_head_forward.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
-    for f in ("corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
+    for f in ("corr_ondemand_lookup_conv", "corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
               "corr_flow_head_forward", "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
               "corr_enc_join_affine", "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
@@ -668,6 +670,25 @@ def ondemand_lookup(workspace, coords, D, levels, radius, out, flags=0):
         raise ValueError(f"out has {out.numel()} floats, the lookup writes {B}x{levels * K}x{H * W}")
     with torch.cuda.device(coords.device):
         _check(lib.corr_ondemand_lookup(ws, c, B, D, H, W, levels, radius, flags, o, _stream(coords)))
+
+
+def ondemand_lookup_conv(workspace, coords, D, levels, radius, packed, bias, out, relu=True, flags=0):
+    """corr_ondemand_lookup_conv: coords [B, 2, H, W] -> out [B, 256, H, W] = relu(convc1(the on-demand
+    lookup)) from a prepared workspace of the same B, D, H, W, levels and lookup_conv_weights' pack,
+    in one launch."""
+    B, _, H, W = coords.shape
+    lib = load()
+    # sizes first: they need no device, and a short buffer must never reach the kernel
+    if workspace.numel() * 4 < lib.corr_ondemand_workspace(B, D, H, W, levels):
+        raise ValueError("workspace is smaller than corr_ondemand_workspace for these sizes")
+    if out.numel() != B * 256 * H * W:
+        raise ValueError(f"out has {out.numel()} floats, the fused lookup writes {B}x256x{H * W}")
+    ws, c, o = _dev(workspace, "workspace"), _dev(coords, "coords"), _dev(out, "out")
+    pw = _pack_arg(packed, lib.corr_lookup_conv_weights_bytes(), coords.device, "corr_ondemand_lookup_conv")
+    bs = _bias_arg(bias, 256, coords.device, optional=False)
+    with torch.cuda.device(coords.device):
+        _check(lib.corr_ondemand_lookup_conv(ws, c, B, D, H, W, levels, radius, flags, pw, bs, int(bool(relu)), o,
+                                             _stream(coords)))
 
 
 def ondemand_bwd_workspace(B, D, H, W, levels, radius, device):

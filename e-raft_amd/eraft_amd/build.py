@@ -16,7 +16,8 @@ OUT_DIR = os.path.join(PKG, "_build")
 SO_NAME = "libcorr_mi355x.so"
 SO_PATH = os.path.join(OUT_DIR, SO_NAME)
 SOURCES = ["corr_build.hip", "corr_build_split.hip", "corr_build_bf16.hip", "corr_lookup.hip", "corr_lookup_conv.hip",
-           "corr_lookup_bwd.hip", "corr_lookup_fold.hip", "corr_ondemand.hip", "corr_ondemand_bwd.hip", "corr_bwd.hip",
+           "corr_lookup_bwd.hip", "corr_lookup_fold.hip", "corr_ondemand.hip", "corr_ondemand_conv.hip", "corr_ondemand_bwd.hip",
+           "corr_bwd.hip",
            "corr_bwd_split.hip", "corr_splat.hip", "corr_upsample.hip", "corr_voxel.hip", "corr_gru.hip",
            "corr_conv.hip", "corr_enc_front.hip", "corr_mask_upsample.hip", "corr_flow.hip",
            "corr_api.cpp"]

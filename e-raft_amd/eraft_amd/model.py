@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .corr import CorrBlock
-from .ondemand import OnDemandCorrBlock
+from .ondemand import OnDemandConvCorrBlock, OnDemandCorrBlock
 from .utils import coords_grid
 
 
@@ -344,6 +344,11 @@ class ERAFT(nn.Module):
     # launch per iteration (upsample.py) and the 576-channel mask is never stored.  Default off
     # (DESIGN §17 has the measurements); training always runs the torch code.
     fuse_mask_upsample = os.environ.get("ERAFT_AMD_FUSE_UPSAMPLE", "0") == "1"
+    # ERAFT_AMD_ONDEMAND_FUSE_CONV=1: with alternate_corr the block is OnDemandConvCorrBlock, whose
+    # lookup_conv is one corr_ondemand_lookup_conv launch at inference (no 324-channel lookup in
+    # HBM, no torch convc1); under autograd it is the unfused composition.  Default off (DESIGN §21
+    # has the measurements).
+    fuse_ondemand_conv = os.environ.get("ERAFT_AMD_ONDEMAND_FUSE_CONV", "0") == "1"
 
     def __init__(self, config, n_first_channels):
         super().__init__()
@@ -401,8 +406,9 @@ class ERAFT(nn.Module):
         image2 = self.image_padder.pad(image2).contiguous()
         fmap1, fmap2 = self.fnet([image1, image2])
         if self.alternate_corr:
-            corr_fn = OnDemandCorrBlock(fmap1.float(), fmap2.float(), num_levels=self.corr_levels,
-                                        radius=self.corr_radius, train=torch.is_grad_enabled())
+            block = OnDemandConvCorrBlock if self.fuse_ondemand_conv else OnDemandCorrBlock
+            corr_fn = block(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius,
+                            train=torch.is_grad_enabled())
         else:
             corr_fn = CorrBlock(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius)
         net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)

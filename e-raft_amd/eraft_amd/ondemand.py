@@ -8,6 +8,11 @@ call computes just the correlation entries its taps touch (corr_ondemand_lookup)
 pyramid does not fit (large maps, large batches); CorrBlock stays the default.  The block has no
 corr_pyramid and no lookup_conv.
 
+OnDemandConvCorrBlock is the same block with CorrBlock's lookup_conv(coords, weight, bias): at
+inference relu(convc1(lookup)) is one launch (corr_ondemand_lookup_conv) and the 324-channel
+lookup is never stored; where autograd would record it is the unfused composition.  ERAFT builds
+it with alternate_corr and ERAFT_AMD_ONDEMAND_FUSE_CONV=1 (default off).
+
 train=True puts the block in the autograd graph (gradients to fmap1 / fmap2 only; coords are
 detached, as in CorrBlock), following corr.py's pattern: the prepare is an autograd function whose
 output is a token, every lookup is an autograd function of the token whose backward only stashes
@@ -19,9 +24,10 @@ the backward workspace is allocated in the backward.
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
 
 from . import _lib
-from .corr import _validate_fmaps
+from .corr import _validate_fmaps, _weight_pack
 
 
 class _OdState:
@@ -123,4 +129,32 @@ class OnDemandCorrBlock:
         K = (2 * self.radius + 1) ** 2
         out = torch.empty((B, self.num_levels * K, H, W), dtype=torch.float32, device=coords.device)
         _lib.ondemand_lookup(self._ws, coords, self._D, self.num_levels, self.radius, out, self.flags)
+        return out
+
+
+class OnDemandConvCorrBlock(OnDemandCorrBlock):
+    """OnDemandCorrBlock with CorrBlock.lookup_conv: the lookup fused with the motion encoder's
+    first layer (radius 4, at most 4 levels)."""
+
+    def lookup_conv(self, coords, weight, bias, relu=True):
+        """relu(convc1(self(coords))) (update.py:68,75) without materialising the lookup output.
+        weight: convc1.weight [256, L*K, 1, 1]; bias [256].  One corr_ondemand_lookup_conv launch
+        under no_grad or when nothing requires grad; where autograd would record (a train=True
+        block with grad enabled, or a weight / bias that requires grad) it is the unfused
+        composition, bit for bit — there is no fused backward."""
+        self._check_coords(coords)
+        B, _, H, W = coords.shape
+        K = (2 * self.radius + 1) ** 2
+        C = self.num_levels * K
+        if tuple(weight.shape) not in ((256, C, 1, 1), (256, C)) or tuple(bias.shape) != (256,):
+            raise ValueError(f"lookup_conv needs weight [256, {C}, 1, 1] and bias [256] "
+                             f"(got {tuple(weight.shape)}, {tuple(bias.shape)})")
+        if torch.is_grad_enabled() and (self._token is not None or weight.requires_grad or bias.requires_grad):
+            out = F.conv2d(self(coords), weight.reshape(256, C, 1, 1), bias)
+            return F.relu(out) if relu else out
+        coords = coords.detach().contiguous()
+        packed = _weight_pack(weight)  # CorrBlock.lookup_conv's pack and cache entry
+        out = torch.empty((B, 256, H, W), dtype=torch.float32, device=coords.device)
+        _lib.ondemand_lookup_conv(self._ws, coords, self._D, self.num_levels, self.radius, packed,
+                                  bias.detach().contiguous().float(), out, relu, self.flags)
         return out

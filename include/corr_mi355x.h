@@ -401,6 +401,36 @@ int corr_lookup_conv(const float *const *pyr, const float *coords, int B, int H,
                      float *out, void *stream);
 
 /*
+ * The ON-DEMAND lookup fused with the same consumer: out[b][o][h][w] = (relu?)(bias[o] +
+ * sum_c weight[o][c] * lookup[b][c][h][w]) where lookup = what corr_ondemand_lookup writes for the
+ * same workspace, coords and flags — in one launch, the [B][levels*81][H][W] lookup is never
+ * stored.  workspace: as prepared by corr_ondemand_prepare for the same B, D, H, W, levels;
+ * packed_weight: corr_lookup_conv_weights' pack (the same buffer serves corr_lookup_conv);
+ * bias [256]; out [B][256][H][W], overwritten.  flags as corr_ondemand_lookup's: the route (tiled
+ * / general) is chosen per 8x8 block of queries and level from the coordinates only, and
+ * CORR_ONDEMAND_GENERAL forces the general routine for every block.  radius 4, levels <= 4
+ * (E-RAFT); CORR_EUNSUPPORTED otherwise.  Inference only: there is no fused backward (compose
+ * corr_ondemand_lookup with the convolution for training).
+ *
+ * Accuracy contract.  The values entering the convolution equal corr_ondemand_lookup's bit for
+ * bit (same routines, same route choice, same summation order), so a weight that selects single
+ * channels returns them exactly.  The convolution is corr_lookup_conv's: each fp32 product
+ * weight * lookup is formed from the exact three-piece bf16 splits of both factors (x = hi + mid +
+ * lo) as six piece products on v_mfma_f32_16x16x32_bf16 with fp32 accumulation — no narrower
+ * than fp32, no scales.  Summation order per output: c = l*81 + i*9 + j ascending, padded with
+ * zeros to 352, in 11 steps of 32 channels; within a step and across steps the leading products
+ * (hi * hi) accumulate in one fp32 register and the five smaller ones (lo*hi, hi*lo, mid*mid,
+ * mid*hi, hi*mid, in that order) in a second; out = (first is infinite ? first : first + second) +
+ * bias, then ReLU as torch's (a NaN stays a NaN).  Against relu(conv2d(lookup)) in fp64: within
+ * 1e-5 of the largest output (measured ~2e-7).  A non-finite lookup value (NaN coordinates do
+ * not give one; non-finite features may) reaches all 256 outputs of its query.  Deterministic:
+ * no atomics, reruns are bit-identical.
+ */
+int corr_ondemand_lookup_conv(const void *workspace, const float *coords, int B, int D, int H, int W, int levels,
+                              int radius, int flags, const void *packed_weight, const float *bias, int relu,
+                              float *out /* [B][256][H][W] */, void *stream);
+
+/*
  * Training backward of corr_lookup_conv (autograd of update.py:68,75 through corr.py:29-50).
  * grad_out = dL/d out [B][256][H][W]; with relu, g' = grad_out where out > 0 (or out is NaN),
  * else 0 (torch's threshold backward; `out` is the forward's output, unused without relu).

@@ -11,8 +11,18 @@ difference from CorrBlock's.  Prints one JSON document; --json also writes it to
 (corr_ondemand_backward / corr_backward) with coherent coordinates and gauss upstream gradients,
 on-demand against CorrBlock (where the pyramid and its gradient fit) in the same way; also the
 on-demand step's split: forward only, and the backward to fmap1 only / fmap2 only (the window
-kernel alone / the window kernel without dF1 plus the dP gather)."""
+kernel alone / the window kernel without dF1 plus the dP gather).
+    python tools/bench_ondemand.py --conv [--sizes ...] [--json profiles/ondemand_conv_bench.json]
+--conv: one GRU iteration's lookup + convc1 + ReLU, 12 iterations (12 coordinate fields) per graph:
+unfused (corr_ondemand_lookup + F.conv2d + ReLU) against fused (corr_ondemand_lookup_conv) and,
+where the pyramid fits, CorrBlock's corr_lookup_conv for scale; us per iteration, each variant's
+peak allocation during one eager iteration, and fused against unfused (norm-relative).
+--variant-lib PATH times a second build of the library as "fused_variant" in the same process
+(the other form of the product); --build-variant makes that build first: corr_ondemand_conv.hip
+with -DCORR_OD_CONV_PRESPLIT=<the form that is not the default>, linked with the package's
+objects into tools/_build/ (run it where the package was built)."""
 import argparse
+import ctypes
 import json
 import math
 import os
@@ -215,17 +225,143 @@ def bench_train(name, trials, dev):
     return res
 
 
+def build_variant():
+    """The library with the other form of the fused product, for --variant-lib."""
+    import re
+    import subprocess
+    from eraft_amd import build
+    build.build_library()
+    src = open(os.path.join(build.SRC, "corr_ondemand_conv.hip")).read()
+    default = int(re.search(r"#define CORR_OD_CONV_PRESPLIT (\d)", src).group(1))
+    out_dir = os.path.join(ROOT, "tools", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    obj = os.path.join(out_dir, "corr_ondemand_conv_variant.o")
+    so = os.path.join(out_dir, "libcorr_mi355x_variant.so")
+    flags = [f for f in build.FLAGS if f != "-shared"]
+    subprocess.run([build.HIPCC, *flags, f"-DCORR_OD_CONV_PRESPLIT={1 - default}", "-c", "-o", obj,
+                    os.path.join(build.SRC, "corr_ondemand_conv.hip")], check=True)
+    objs = [obj if s == "corr_ondemand_conv.hip" else os.path.join(build.OBJ_DIR, os.path.splitext(s)[0] + ".o")
+            for s in build.SOURCES]
+    subprocess.run([build.HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", so, *objs], check=True)
+    return so
+
+
+def bench_conv(name, trials, dev, variant):
+    """One iteration's lookup + convc1 + ReLU at one size: us per iteration and peak allocation."""
+    import torch.nn.functional as F
+    H, W, fits = SIZES[name]
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    f1 = torch.randn(B, D, H, W, device=dev, generator=gen)
+    f2 = torch.randn(B, D, H, W, device=dev, generator=gen)
+    K = (2 * R + 1) ** 2
+    w = 0.05 * torch.randn(256, L * K, 1, 1, device=dev, generator=gen)
+    bias = 0.1 * torch.randn(256, device=dev, generator=gen)
+    packed = _lib.lookup_conv_weights(w)
+    ws = _lib.ondemand_workspace(B, D, H, W, L, dev)
+    _lib.ondemand_prepare(f1, f2, L, ws)
+    pyr = None
+    if fits:
+        pyr = _alloc_pyramid(B, H, W, L, f1)
+        _lib.build(f1, f2, pyr, _lib.default_algo(), _lib.build_workspace(f1, f2, _lib.default_algo()))
+    stream = torch.cuda.Stream()
+    res = {"H": H, "W": W, "B": B, "D": D, "levels": L, "radius": R, "iterations_per_graph": ITERS, "kinds": {}}
+
+    def unfused(c):
+        look = torch.empty(B, L * K, H, W, device=dev)
+        _lib.ondemand_lookup(ws, c, D, L, R, look)
+        return F.relu(F.conv2d(look, w, bias))
+
+    def fused(c):
+        out = torch.empty(B, 256, H, W, device=dev)
+        _lib.ondemand_lookup_conv(ws, c, D, L, R, packed, bias, out)
+        return out
+
+    def fused_variant(c):
+        out = torch.empty(B, 256, H, W, device=dev)
+        rc = variant.corr_ondemand_lookup_conv(ws.data_ptr(), c.data_ptr(), B, D, H, W, L, R, 0, packed.data_ptr(),
+                                               bias.data_ptr(), 1, out.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, variant.corr_last_error()
+        return out
+
+    def corrblock(c):
+        out = torch.empty(B, 256, H, W, device=dev)
+        _lib.lookup_conv(pyr, c, R, packed, bias, out)
+        return out
+
+    fns = {"unfused": unfused, "fused": fused}
+    if variant is not None:
+        fns["fused_variant"] = fused_variant
+    if fits:
+        fns["corrblock_lookup_conv"] = corrblock
+    for kind in ("coherent", "sigma4"):
+        coords = make_coords(kind, H, W, dev, gen)
+        graphs, peaks, outs, keep = {}, {}, {}, []
+        for n, fn in fns.items():
+            with torch.cuda.stream(stream):
+                fn(coords[-1])  # MIOpen picks its kernel outside the measurement
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                outs[n] = fn(coords[-1])
+                torch.cuda.synchronize()
+                peaks[n] = (torch.cuda.max_memory_allocated() - base) / 1e6
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr, stream=stream):
+                    keep.append([fn(c) for c in coords])
+            torch.cuda.synchronize()
+            graphs[n] = gr
+        steps = max(3, int(0.3 / (0.5e-3 * max(1.0, H * W / 4800.0))))  # ~0.3 s or more per window
+        times = {n: [] for n in graphs}
+        for t in range(trials + 1):
+            for n, gr in graphs.items():
+                gr.replay()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    gr.replay()
+                torch.cuda.synchronize()
+                if t:  # trial 0 warms every variant
+                    times[n].append((time.perf_counter() - t0) / (steps * ITERS) * 1e6)
+        entry = {}
+        for n, v in times.items():
+            v = sorted(v)
+            entry[n] = {"iteration_us_median": round(v[len(v) // 2], 2), "iteration_us_min": round(v[0], 2),
+                        "iteration_us_max": round(v[-1], 2), "peak_alloc_mb": round(peaks[n], 2)}
+        entry["fused_vs_unfused_rel"] = norm_rel(outs["fused"], outs["unfused"])
+        if variant is not None:
+            entry["fused_variant_vs_fused_rel"] = norm_rel(outs["fused_variant"], outs["fused"])
+        if fits:
+            entry["fused_vs_corrblock_rel"] = norm_rel(outs["fused"], outs["corrblock_lookup_conv"])
+        entry["graph_replays_per_window"] = steps
+        res["kinds"][kind] = entry
+        del graphs, keep, outs
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="dsec,hires1280,hires1920,uhd")
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--json", default=None)
     ap.add_argument("--train", action="store_true", help="training steps: forward + backward to both maps")
+    ap.add_argument("--conv", action="store_true", help="one iteration's lookup + convc1 + ReLU, fused vs unfused")
+    ap.add_argument("--variant-lib", default=None, help="--conv: a second build of the library, timed beside")
+    ap.add_argument("--build-variant", action="store_true", help="build that library (no GPU needed) and exit")
     a = ap.parse_args()
+    if a.build_variant:
+        print(build_variant())
+        return
     if not torch.cuda.is_available():
         sys.exit("bench_ondemand needs an MI355X (no CPU fallback)")
     dev = torch.device("cuda", 0)
-    if a.train:
+    if a.conv:
+        variant = _lib.load(a.variant_lib) if a.variant_lib else None
+        doc = {"device": torch.cuda.get_device_name(0),
+               "step": "one iteration's lookup + convc1 + ReLU; 12 iterations per HIP graph, us per iteration",
+               "sizes": {n: bench_conv(n, a.trials, dev, variant) for n in a.sizes.split(",")}}
+    elif a.train:
         doc = {"device": torch.cuda.get_device_name(0),
                "step": "prepare/build + 12 lookups + backward to both maps, one HIP graph",
                "sizes": {n: bench_train(n, a.trials, dev) for n in a.sizes.split(",")}}
