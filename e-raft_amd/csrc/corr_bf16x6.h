@@ -59,7 +59,9 @@ __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
 
 // One K step of the forward kernels: the six piece products of W (wa = hi, mid, lo A fragments)
 // and x (xb = hi, mid, lo B fragments), in THE order of the family — every forward kernel's
-// arithmetic contract, which their parity tests pin bit for bit:
+// arithmetic contract, pinned bit for bit by tests/test_bf16x6_family.py (inputs on which each
+// output is one exactly representable product, so every piece product and every pack's pieces
+// show in the last bit; its model of this function is tests/_bf16x6.py):
 //   acs += wl xh;  acs += wh xl;  acs += wm xm;  acs += wm xh;  acs += wh xm;     acc += wh xh
 // The five smaller products go to acs, smallest first, the leading one to acc; split_sum
 // (corr_common.h) joins the two at the end.  (The lookup-conv backward's two GEMMs use orders of

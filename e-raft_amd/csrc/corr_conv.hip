@@ -39,8 +39,8 @@
 // norm, merged by enc_finalize_kernel; enc_join_kernel is the block's normalise + add + ReLU.
 // <1, false, false> is the kernel described above, unchanged in its arithmetic.
 //
-// Non-finite inputs are not parity-checked (an infinite activation meets the zero mid / lo
-// pieces of the weights); finite inputs give finite outputs.
+// Non-finite inputs give fp32's pattern (an infinite operand splits as (inf, 0, 0) and split_sum
+// keeps the infinite leading sum; tests/test_bf16x6_family.py); finite inputs give finite outputs.
 #include <type_traits>
 
 #include "corr_bf16x6.h"

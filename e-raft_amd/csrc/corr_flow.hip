@@ -32,7 +32,8 @@
 //
 // Every load is unconditional, from an address clamped into the same map; a zero is applied to
 // the loaded value (or the product) afterwards.  No atomics, no scratch, nothing allocated.
-// Non-finite inputs are not parity-checked (corr_conv.hip's note applies).
+// Non-finite inputs: the head gives fp32's pattern (corr_conv.hip's note applies); the encoder is
+// not parity-checked on them.
 #include "corr_bf16x6.h"
 #include "corr_common.h"
 

@@ -29,8 +29,8 @@
 // pre-split once (gru_pack_kernel) into A-fragment order [16-row block][chunk][tap][piece][lane]
 // and streamed from L2 four K steps ahead.  No atomics, no scratch, nothing allocated.
 //
-// Non-finite inputs are not parity-checked (an infinite activation meets the zero mid / lo
-// pieces of the weights); finite inputs give finite outputs.
+// Non-finite inputs give fp32's pattern (an infinite operand splits as (inf, 0, 0) and split_sum
+// keeps the infinite leading sum; tests/test_bf16x6_family.py); finite inputs give finite outputs.
 #include <cmath>
 
 #include "corr_bf16x6.h"

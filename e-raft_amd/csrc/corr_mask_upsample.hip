@@ -30,7 +30,7 @@
 // clamped addresses inside the pixel's own map and zeroed afterwards.  No atomics, no scratch,
 // no workspace.
 //
-// Non-finite inputs are not parity-checked (corr_conv.hip's note applies).
+// Non-finite inputs give fp32's pattern (corr_conv.hip's note applies).
 #include "corr_bf16x6.h"
 #include "corr_common.h"
 
