@@ -607,12 +607,19 @@ size_t corr_gru_workspace(int B, int hidden, int H, int W) {
     return gru_workspace(B, hidden, H, W);
 }
 
-int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
-                       const void *packed, const float *bz, const float *br, const float *bq, void *workspace,
-                       size_t workspace_bytes, float *h_out, void *stream) {
-    static const char *fn = "corr_gru_half_step";
+// CORR_PREC_*: refused first, so that no other argument is looked at under an unknown mode.
+static int check_precision(const char *fn, int precision) {
+    if (precision_supported(precision)) return CORR_OK;
+    return fail(CORR_EINVAL, "%s: precision must be CORR_PREC_BF16X6 (0), _BF16X3 (1) or _BF16 (2) (got %d)", fn,
+                precision);
+}
+
+static int gru_half_step(const char *fn, const float *h, const float *x, int B, int hidden, int input, int H, int W,
+                         int dir, const void *packed, const float *bz, const float *br, const float *bq,
+                         void *workspace, size_t workspace_bytes, float *h_out, void *stream, int precision) {
     g_err[0] = 0;
     int rc;
+    if ((rc = check_precision(fn, precision))) return rc;
     if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if ((rc = check_gru_channels(fn, hidden, input))) return rc;
     if (dir != 0 && dir != 1) return fail(CORR_EINVAL, "%s: dir must be 0 (1x5) or 1 (5x1) (got %d)", fn, dir);
@@ -627,8 +634,22 @@ int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int in
         return fail(CORR_EINVAL, "%s: workspace of %zu bytes needed, got %zu", fn, need, workspace_bytes);
     if ((uintptr_t)workspace % 16) return fail(CORR_EINVAL, "%s: workspace is not 16-byte aligned", fn);
     return hip_status(launch_gru_half_step(h, x, B, hidden, input, H, W, dir, packed, bz, br, bq, workspace, h_out,
-                                           (hipStream_t)stream),
+                                           (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
+                       const void *packed, const float *bz, const float *br, const float *bq, void *workspace,
+                       size_t workspace_bytes, float *h_out, void *stream) {
+    return gru_half_step("corr_gru_half_step", h, x, B, hidden, input, H, W, dir, packed, bz, br, bq, workspace,
+                         workspace_bytes, h_out, stream, CORR_PREC_BF16X6);
+}
+
+int corr_gru_half_step_prec(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
+                            const void *packed, const float *bz, const float *br, const float *bq, void *workspace,
+                            size_t workspace_bytes, float *h_out, int precision, void *stream) {
+    return gru_half_step("corr_gru_half_step_prec", h, x, B, hidden, input, H, W, dir, packed, bz, br, bq, workspace,
+                         workspace_bytes, h_out, stream, precision);
 }
 
 static int check_conv_channels(const char *fn, int cout, int ca, int cb) {
@@ -660,12 +681,12 @@ static bool ranges_overlap(const void *p, long double n, const void *q, long dou
     return a < b + m && b < a + n;
 }
 
-int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W, const void *packed,
-                      const float *bias, int cout, int relu, float *out, int out_channels, int out_offset,
-                      void *stream) {
-    static const char *fn = "corr_conv_forward";
+static int conv_forward(const char *fn, const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
+                        const void *packed, const float *bias, int cout, int relu, float *out, int out_channels,
+                        int out_offset, void *stream, int precision) {
     g_err[0] = 0;
     int rc;
+    if ((rc = check_precision(fn, precision))) return rc;
     if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if ((rc = check_conv_channels(fn, cout, ca, cb))) return rc;
     if (relu != 0 && relu != 1) return fail(CORR_EINVAL, "%s: relu must be 0 or 1 (got %d)", fn, relu);
@@ -681,8 +702,22 @@ int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int 
         return fail(CORR_EINVAL, "%s: out must not overlap in_a or in_b", fn);
     if ((rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_conv_forward(in_a, ca, in_b, cb, B, H, W, packed, bias, cout, relu, out, out_channels,
-                                          out_offset, (hipStream_t)stream),
+                                          out_offset, (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W, const void *packed,
+                      const float *bias, int cout, int relu, float *out, int out_channels, int out_offset,
+                      void *stream) {
+    return conv_forward("corr_conv_forward", in_a, ca, in_b, cb, B, H, W, packed, bias, cout, relu, out, out_channels,
+                        out_offset, stream, CORR_PREC_BF16X6);
+}
+
+int corr_conv_forward_prec(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
+                           const void *packed, const float *bias, int cout, int relu, float *out, int out_channels,
+                           int out_offset, int precision, void *stream) {
+    return conv_forward("corr_conv_forward_prec", in_a, ca, in_b, cb, B, H, W, packed, bias, cout, relu, out,
+                        out_channels, out_offset, stream, precision);
 }
 
 size_t corr_enc_stats_bytes(int B, int cout, int Ho, int Wo) {

@@ -3,6 +3,17 @@
 // split build and backward (the split only) and by the convolution kernels (corr_lookup_conv,
 // corr_ondemand_conv, corr_gru, corr_conv, corr_mask_upsample, corr_enc_front, corr_flow .hip).
 // Internal, not part of the C-ABI.
+//
+// The reduced modes (corr_gru.hip and corr_conv.hip's update-block form, selected per call by the
+// C-ABI's `precision`) keep fewer of split3's pieces per operand, guards included, and multiply
+// only the products among the kept ones (products<NP>() below):
+//   bf16x6 (NP = 3, the default)  hi, mid, lo   six products:   no narrower than fp32
+//   bf16x3 (NP = 2)               hi, mid       three products: operands to 2^-18, the dropped
+//                                               wm xm to 2^-16 relative
+//   bf16   (NP = 1)               hi            one product:    operands to 2^-9 relative
+// The accumulators stay fp32 and the packs are the same in every mode (a reduced mode skips the
+// pieces it does not keep), so an infinite operand still splits as (inf, 0, 0) and the non-finite
+// pattern stays fp32's.
 #pragma once
 
 #include "corr_common.h"
@@ -73,6 +84,27 @@ __device__ __forceinline__ void six(const u32x4 (&wa)[3], const u32x4 (&xb)[3], 
     acs = mfma_bf16(wa[1], xb[0], acs);
     acs = mfma_bf16(wa[0], xb[1], acs);
     acc = mfma_bf16(wa[0], xb[0], acc);
+}
+
+// The K step of a kernel that keeps NP pieces per operand (wa, xb = the first NP of hi, mid, lo).
+// NP = 3 is six() itself.  The orders of the reduced modes are part of the same contract (pinned
+// by tests/test_precision.py):
+//   NP = 2 (bf16x3):  acs += wm xh;  acs += wh xm;     acc += wh xh      (six()'s order without
+//                     the products that hold a lo piece, and without wm xm)
+//   NP = 1 (bf16):    acc += wh xh                                       (acs is not touched: the
+//                     kernel's result is acc alone)
+template <int NP>
+__device__ __forceinline__ void products(const u32x4 (&wa)[NP], const u32x4 (&xb)[NP], f32x4 &acc, f32x4 &acs) {
+    static_assert(NP >= 1 && NP <= 3, "one, two or three pieces");
+    if constexpr (NP == 3) {
+        six(wa, xb, acc, acs);
+    } else {
+        if constexpr (NP == 2) {
+            acs = mfma_bf16(wa[1], xb[0], acs);
+            acs = mfma_bf16(wa[0], xb[1], acs);
+        }
+        acc = mfma_bf16(wa[0], xb[0], acc);
+    }
 }
 
 // A pack kernel's store of one A fragment: dst = this lane's slot of the hi piece, the mid and lo

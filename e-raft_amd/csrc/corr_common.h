@@ -210,16 +210,19 @@ size_t gru_weights_bytes(int hidden, int input);
 size_t gru_workspace(int B, int hidden, int H, int W);
 hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, int hidden, int input, void *packed,
                            hipStream_t s);
+// `precision` (here and in launch_conv_forward): CORR_PREC_* of the C-ABI, the pieces of the split
+// that the products keep (0: hi, mid, lo = bf16x6; 1: hi, mid = bf16x3; 2: hi = bf16; corr_bf16x6.h).
+inline bool precision_supported(int precision) { return precision >= 0 && precision <= 2; }
 hipError_t launch_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
                                 const void *packed, const float *bz, const float *br, const float *bq, void *ws,
-                                float *h_out, hipStream_t s);
+                                float *h_out, hipStream_t s, int precision);
 // 3x3 convolution + bias + ReLU over two input pointers into a channel window (corr_conv.hip).
 bool conv_supported(int cout, int ca, int cb);
 size_t conv_weights_bytes(int cout, int cin);
 hipError_t launch_conv_pack(const float *w, int cout, int cin, void *packed, hipStream_t s);
 hipError_t launch_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
                                const void *packed, const float *bias, int cout, int relu, float *out,
-                               int out_channels, int out_offset, hipStream_t s);
+                               int out_channels, int out_offset, hipStream_t s, int precision);
 // The encoders' residual stages (corr_conv.hip): the same convolution at stride 1 or 2 with norm
 // on load and per-tile statistics, the statistics' merge, and the block's join.
 size_t enc_stats_bytes(int B, int cout, int Ho, int Wo);

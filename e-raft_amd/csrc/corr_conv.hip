@@ -41,6 +41,11 @@
 //
 // Non-finite inputs give fp32's pattern (an infinite operand splits as (inf, 0, 0) and split_sum
 // keeps the infinite leading sum; tests/test_bf16x6_family.py); finite inputs give finite outputs.
+//
+// `precision` (CORR_PREC_*) selects NP for the update block's form <1, false, false>: the reduced
+// modes stage, fetch and multiply only the first two pieces (bf16x3, three products) or the first
+// one (bf16, one product, one accumulator) of both operands, from the same pack (corr_bf16x6.h,
+// DESIGN §23).  The encoder forms keep all three.
 #include <type_traits>
 
 #include "corr_bf16x6.h"
@@ -71,7 +76,9 @@ constexpr int kConvT = 1;                      // 16-row blocks per wave (2 meas
 constexpr int kConvOB = 32 * kConvT;           // output rows per workgroup
 constexpr int kConvXS = 16 + 4;                // words per LDS position: 16 channel pairs + pad (16-B rows)
 constexpr int kConvTaps = 9;
-constexpr int kConvWaves = 2;                  // waves per SIMD the kernel is compiled for (<= 256 registers)
+// Waves per SIMD the kernel is compiled for, by the pieces it keeps (2: <= 256 registers; 3: <= 168).
+// One piece needs 144 registers; two pieces need 186 and spill at 168.
+constexpr int conv_waves(int np) { return np == 1 ? 3 : 2; }
 constexpr int kConvRing = 6;                   // weight ring slots; divides the 18 K steps of a chunk pair
 constexpr int kConvAhead = 5;                  // K steps the weight fragments run ahead (< kConvRing)
 constexpr int kConvMaxCin = 1024;              // conv_supported's bound (the norm-on-load table in LDS)
@@ -120,11 +127,15 @@ struct ConvArgs {
 // outside the map is applied after it: the padding is zero in the normalised domain.  STATS: no
 // ReLU, and the workgroup leaves (sum, M2 about the tile's own mean) of its valid pixels per
 // output channel (header: corr_enc_conv_forward).
-template <int STRIDE, bool NORM_IN, bool STATS>
-__global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
+// NP: the pieces kept per operand (3 = bf16x6; 2 = bf16x3 and 1 = bf16 for the update block's
+// <1, false, false> form only: products<NP>, corr_bf16x6.h).  The pack is the same for every NP:
+// a reduced mode skips the 1-KB runs of the pieces it drops.
+template <int STRIDE, bool NORM_IN, bool STATS, int NP = 3>
+__global__ __launch_bounds__(kConvNT, conv_waves(NP)) void conv_kernel(ConvArgs g) {
+    static_assert(NP == 3 || (STRIDE == 1 && !NORM_IN && !STATS), "the encoder forms keep all three pieces");
     using G = ConvGeo<STRIDE>;
     constexpr int kConvPW = G::PW, kConvNPOS = G::NPOS, kConvStage = G::Stage, kConvNLD = G::NLD;
-    __shared__ __attribute__((aligned(16))) unsigned xs[3][kConvNPOS][kConvXS];
+    __shared__ __attribute__((aligned(16))) unsigned xs[NP][kConvNPOS][kConvXS];
     __shared__ float nrm[NORM_IN ? 2 * kConvMaxCin : 1];  // scale | shift of this batch item's channels
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int H = g.H, W = g.W;
@@ -199,13 +210,13 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
 
     // ---- A fragments: row blocks ob0 .. ob0 + kConvT - 1 of the pack, K step s = 9 chunk + tap ----
     const int ob0 = (int)blockIdx.y * (kConvOB / 16) + kConvT * (w & 1);
-    auto load_a = [&](u32x4 (&wa)[kConvT][3], int s) {
+    auto load_a = [&](u32x4 (&wa)[kConvT][NP], int s) {
         s = s < NS ? s : NS - 1;  // the last steps re-read the last fragment
 #pragma unroll
         for (int t = 0; t < kConvT; ++t) {
             const size_t base = ((size_t)(ob0 + t) * NS + s) * 3 * 64 + lane;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) wa[t][p] = g.frag[base + 64 * p];
+            for (int p = 0; p < NP; ++p) wa[t][p] = g.frag[base + 64 * p];
         }
     };
 
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
     // constant), the activations two chunks ahead in two register sets: at DSEC a CU holds one or
     // two workgroups, too few to hide an L2 round trip per step.  (Stride 2 stages 2.75 times as
     // many values per chunk and keeps one set, one chunk ahead.)
-    u32x4 wa[kConvRing][kConvT][3];
+    u32x4 wa[kConvRing][kConvT][NP];
     float va[kConvNLD][2];
     [[maybe_unused]] float vb[G::Ahead == 2 ? kConvNLD : 1][2];
     load_chunk(0, va);
@@ -248,8 +259,8 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
             if (STRIDE == 1 ? i + 1 < kConvNLD || tid + kConvNT * i < kConvStage
                             : ib + 1 < G::NPP || lane + 64 * ib < kConvNPOS) {
                 xs[0][ps[ib]][kpi] = hi;
-                xs[1][ps[ib]][kpi] = mid;
-                xs[2][ps[ib]][kpi] = lo;
+                if constexpr (NP > 1) xs[1][ps[ib]][kpi] = mid;
+                if constexpr (NP > 2) xs[2][ps[ib]][kpi] = lo;
             }
         }
         __syncthreads();
@@ -258,17 +269,17 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
         for (int tap = 0; tap < kConvTaps; ++tap) {
             load_a(wa[(S0 + tap + kConvAhead) % kConvRing], ch * kConvTaps + tap + kConvAhead);
             const int tp = (tap / 3) * kConvPW + tap % 3;
-            u32x4 xb[2][3];
+            u32x4 xb[2][NP];
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int p = 0; p < 3; ++p)
+                for (int p = 0; p < NP; ++p)
                     xb[c][p] = *reinterpret_cast<const u32x4 *>(
                         &xs[p][STRIDE * ((j0 + c) * kConvPW + fr) + tp][fk]);
 #pragma unroll
             for (int t = 0; t < kConvT; ++t)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) six(wa[(S0 + tap) % kConvRing][t], xb[c], acc[t][c], acs[t][c]);
+                for (int c = 0; c < 2; ++c) products<NP>(wa[(S0 + tap) % kConvRing][t], xb[c], acc[t][c], acs[t][c]);
         }
         __syncthreads();
     };
@@ -299,7 +310,7 @@ __global__ __launch_bounds__(kConvNT, kConvWaves) void conv_kernel(ConvArgs g) {
                 for (int r = 0; r < 4; ++r) {
                     const int row = (int)blockIdx.y * kConvOB + 16 * kConvT * (w & 1) + 16 * t + 4 * (lane >> 4) + r;
                     if (row >= g.cout) continue;  // a padding row of the pack
-                    float v = split_sum(acc[t][c][r], acs[t][c][r]);
+                    float v = NP == 1 ? acc[t][c][r] : split_sum(acc[t][c][r], acs[t][c][r]);
                     if (g.bias) v = v + g.bias[row];
                     if (g.relu) v = v < 0.f ? 0.f : v;
                     g.out[((size_t)b * g.oc + g.off + row) * HWo + n] = v;
@@ -413,10 +424,10 @@ __global__ __launch_bounds__(256) void enc_join_kernel(const float *y, const flo
 
 constexpr int conv_rows(int cout) { return (cout + kConvPad - 1) / kConvPad * kConvPad; }
 
-template <int STRIDE, bool NORM_IN, bool STATS>
+template <int STRIDE, bool NORM_IN, bool STATS, int NP = 3>
 hipError_t launch_conv(const ConvArgs &g, hipStream_t s) {
     const dim3 grid((unsigned)g.B * g.tx * g.ty, conv_rows(g.cout) / kConvOB);
-    hipLaunchKernelGGL((conv_kernel<STRIDE, NORM_IN, STATS>), grid, dim3(kConvNT), 0, s, g);
+    hipLaunchKernelGGL((conv_kernel<STRIDE, NORM_IN, STATS, NP>), grid, dim3(kConvNT), 0, s, g);
     return hipGetLastError();
 }
 
@@ -439,8 +450,8 @@ hipError_t launch_conv_pack(const float *w, int cout, int cin, void *packed, hip
 
 hipError_t launch_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
                                const void *packed, const float *bias, int cout, int relu, float *out,
-                               int out_channels, int out_offset, hipStream_t s) {
-    if (!conv_supported(cout, ca, cb)) return hipErrorInvalidValue;
+                               int out_channels, int out_offset, hipStream_t s, int precision) {
+    if (!conv_supported(cout, ca, cb) || !precision_supported(precision)) return hipErrorInvalidValue;
     ConvArgs g{};
     g.a = in_a, g.b = cb > 0 ? in_b : in_a, g.bias = bias;
     g.frag = static_cast<const u32x4 *>(packed);
@@ -448,7 +459,11 @@ hipError_t launch_conv_forward(const float *in_a, int ca, const float *in_b, int
     g.B = B, g.ca = ca, g.cb = cb, g.H = H, g.W = W, g.cout = cout, g.relu = relu;
     g.oc = out_channels, g.off = out_offset;
     g.tx = (W + kConvTW - 1) / kConvTW, g.ty = (H + kConvTH - 1) / kConvTH;
-    return launch_conv<1, false, false>(g, s);
+    switch (precision) {
+        case 1: return launch_conv<1, false, false, 2>(g, s);
+        case 2: return launch_conv<1, false, false, 1>(g, s);
+        default: return launch_conv<1, false, false>(g, s);
+    }
 }
 
 static int enc_out(int n, int stride) { return (n - 1) / stride + 1; }

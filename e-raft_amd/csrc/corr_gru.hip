@@ -31,6 +31,10 @@
 //
 // Non-finite inputs give fp32's pattern (an infinite operand splits as (inf, 0, 0) and split_sum
 // keeps the infinite leading sum; tests/test_bf16x6_family.py); finite inputs give finite outputs.
+//
+// `precision` (CORR_PREC_*) selects the kernel's NP: the reduced modes stage, fetch and multiply
+// only the first two pieces (bf16x3, three products) or the first one (bf16, one product, one
+// accumulator) of both operands, from the same pack (corr_bf16x6.h).
 #include <cmath>
 
 #include "corr_bf16x6.h"
@@ -46,7 +50,9 @@ constexpr int kGruOB = 64;                  // output rows per workgroup
 constexpr int kGruNT = 256;                 // threads
 constexpr int kGruXS = 16 + 4;              // words per LDS position: 16 channel pairs + pad (16-B rows)
 constexpr int kGruTaps = 5;
-constexpr int kGruWaves = 2;                // waves per SIMD the kernel is compiled for (<= 256 registers)
+// Waves per SIMD the kernel is compiled for, by the pieces it keeps (2: <= 256 registers; 3: <= 168).
+// One piece needs 132 .. 152 registers; two pieces need 208 .. 224 and spill at 168.
+constexpr int gru_waves(int np) { return np == 1 ? 3 : 2; }
 constexpr int kGruAhead = 4;                // K steps the weight fragments run ahead (< kGruTaps)
 constexpr int kGruBlocks = 3 * kGruH / 16;  // 16-row blocks of the pack: z, r, q
 
@@ -95,10 +101,12 @@ struct GruArgs {
     int B, input, H, W, tx, ty;
 };
 
-template <bool GATES, int DIR>
-__global__ __launch_bounds__(kGruNT, kGruWaves) void gru_kernel(GruArgs g) {
+// NP: the pieces kept per operand (3 = bf16x6, 2 = bf16x3, 1 = bf16; products<NP>, corr_bf16x6.h).
+// The pack is the same for every NP: a reduced mode skips the 1-KB runs of the pieces it drops.
+template <bool GATES, int DIR, int NP>
+__global__ __launch_bounds__(kGruNT, gru_waves(NP)) void gru_kernel(GruArgs g) {
     using T = GruTile<DIR>;
-    __shared__ __attribute__((aligned(16))) unsigned xs[3][T::NPOS][kGruXS];
+    __shared__ __attribute__((aligned(16))) unsigned xs[NP][T::NPOS][kGruXS];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int H = g.H, W = g.W;
     const size_t HW = (size_t)H * W;
@@ -136,13 +144,13 @@ __global__ __launch_bounds__(kGruNT, kGruWaves) void gru_kernel(GruArgs g) {
 
     // ---- A fragments: row blocks ob0, ob0 + 1 of the pack, K step s = 5 chunk + tap ----
     const int ob0 = (GATES ? 0 : 2 * kGruH / 16) + (int)blockIdx.y * (kGruOB / 16) + 2 * (w & 1);
-    auto load_a = [&](u32x4 (&wa)[2][3], int s) {
+    auto load_a = [&](u32x4 (&wa)[2][NP], int s) {
         s = s < NS ? s : NS - 1;  // the last steps re-read the last fragment
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const size_t base = ((size_t)(ob0 + t) * NS + s) * 3 * 64 + lane;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) wa[t][p] = g.frag[base + 64 * p];
+            for (int p = 0; p < NP; ++p) wa[t][p] = g.frag[base + 64 * p];
         }
     };
 
@@ -156,7 +164,7 @@ __global__ __launch_bounds__(kGruNT, kGruWaves) void gru_kernel(GruArgs g) {
     // The weights run kGruAhead K steps ahead of the products in a ring of one slot per tap (step
     // s = 5 chunk + tap lives in slot tap), the activations two chunks ahead in two register
     // sets: at DSEC a CU holds one or two workgroups, too few to hide an L2 round trip per step.
-    u32x4 wa[kGruTaps][2][3];
+    u32x4 wa[kGruTaps][2][NP];
     float va[T::NLD][2], vb[T::NLD][2];
     load_chunk(0, va);
     load_chunk(NC > 1 ? 1 : 0, vb);
@@ -169,24 +177,24 @@ __global__ __launch_bounds__(kGruNT, kGruWaves) void gru_kernel(GruArgs g) {
             const bool in = (inmap >> i) & 1;
             split3(in ? v[i][0] : 0.f, in ? v[i][1] : 0.f, hi, mid, lo);
             xs[0][ps[i]][kp[i]] = hi;
-            xs[1][ps[i]][kp[i]] = mid;
-            xs[2][ps[i]][kp[i]] = lo;
+            if constexpr (NP > 1) xs[1][ps[i]][kp[i]] = mid;
+            if constexpr (NP > 2) xs[2][ps[i]][kp[i]] = lo;
         }
         __syncthreads();
         load_chunk(ch + 2 < NC ? ch + 2 : NC - 1, v);  // (past the end: a harmless re-read)
 #pragma unroll
         for (int tap = 0; tap < kGruTaps; ++tap) {
             load_a(wa[(tap + kGruAhead) % kGruTaps], ch * kGruTaps + tap + kGruAhead);
-            u32x4 xb[2][3];
+            u32x4 xb[2][NP];
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int p = 0; p < 3; ++p)
+                for (int p = 0; p < NP; ++p)
                     xb[c][p] = *reinterpret_cast<const u32x4 *>(&xs[p][(j0 + c) * T::PW + fr + tap * T::TSTEP][fk]);
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) six(wa[tap][t], xb[c], acc[t][c], acs[t][c]);
+                for (int c = 0; c < 2; ++c) products<NP>(wa[tap][t], xb[c], acc[t][c], acs[t][c]);
         }
         __syncthreads();
     };
@@ -213,7 +221,7 @@ __global__ __launch_bounds__(kGruNT, kGruWaves) void gru_kernel(GruArgs g) {
                 const int row = (int)blockIdx.y * kGruOB + 32 * (w & 1) + 16 * t + 4 * (lane >> 4) + r;
                 const int o = row & (kGruH - 1);
                 const size_t at = ((size_t)b * kGruH + o) * HW + n;
-                const float s = split_sum(acc[t][c][r], acs[t][c][r]);
+                const float s = NP == 1 ? acc[t][c][r] : split_sum(acc[t][c][r], acs[t][c][r]);
                 if constexpr (GATES) {
                     if (row < kGruH) {
                         g.z[at] = 1.0f / (1.0f + expf(-(s + g.b0[o])));
@@ -230,11 +238,21 @@ __global__ __launch_bounds__(kGruNT, kGruWaves) void gru_kernel(GruArgs g) {
     }
 }
 
-template <bool GATES>
+template <bool GATES, int NP>
 void launch_gru(const GruArgs &g, int dir, hipStream_t s) {
     const dim3 grid((unsigned)g.B * g.tx * g.ty, (GATES ? 2 : 1) * kGruH / kGruOB);
-    if (dir == 0) hipLaunchKernelGGL((gru_kernel<GATES, 0>), grid, dim3(kGruNT), 0, s, g);
-    else hipLaunchKernelGGL((gru_kernel<GATES, 1>), grid, dim3(kGruNT), 0, s, g);
+    if (dir == 0) hipLaunchKernelGGL((gru_kernel<GATES, 0, NP>), grid, dim3(kGruNT), 0, s, g);
+    else hipLaunchKernelGGL((gru_kernel<GATES, 1, NP>), grid, dim3(kGruNT), 0, s, g);
+}
+
+template <int NP>
+hipError_t launch_gru_pair(GruArgs &g, int dir, const float *bq, hipStream_t s) {
+    launch_gru<true, NP>(g, dir, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    g.a = g.rh, g.b0 = bq, g.b1 = nullptr;
+    launch_gru<false, NP>(g, dir, s);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -263,8 +281,9 @@ hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, in
 
 hipError_t launch_gru_half_step(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
                                 const void *packed, const float *bz, const float *br, const float *bq, void *ws,
-                                float *h_out, hipStream_t s) {
-    if (!gru_supported(hidden, input) || (dir != 0 && dir != 1)) return hipErrorInvalidValue;
+                                float *h_out, hipStream_t s, int precision) {
+    if (!gru_supported(hidden, input) || (dir != 0 && dir != 1) || !precision_supported(precision))
+        return hipErrorInvalidValue;
     GruArgs g{};
     g.x = x;
     g.h = h;
@@ -275,12 +294,11 @@ hipError_t launch_gru_half_step(const float *h, const float *x, int B, int hidde
     g.B = B, g.input = input, g.H = H, g.W = W;
     g.tx = (W + kGruTW - 1) / kGruTW, g.ty = (H + kGruTH - 1) / kGruTH;
     g.a = h, g.b0 = bz, g.b1 = br;
-    launch_gru<true>(g, dir, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    g.a = g.rh, g.b0 = bq, g.b1 = nullptr;
-    launch_gru<false>(g, dir, s);
-    return hipGetLastError();
+    switch (precision) {
+        case 1: return launch_gru_pair<2>(g, dir, bq, s);
+        case 2: return launch_gru_pair<1>(g, dir, bq, s);
+        default: return launch_gru_pair<3>(g, dir, bq, s);
+    }
 }
 
 }  // namespace corr

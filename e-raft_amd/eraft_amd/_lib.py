@@ -41,7 +41,7 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_enc_pw_pack_weights", "corr_enc_pw_forward", "corr_enc_join_affine",
            "corr_flow_enc_weights_bytes", "corr_flow_enc_pack_weights", "corr_flow_enc_forward",
            "corr_flow_head_weights_bytes", "corr_flow_head_pack_weights", "corr_flow_head_forward",
-           "corr_ondemand_lookup_conv")
+           "corr_ondemand_lookup_conv", "corr_gru_half_step_prec", "corr_conv_forward_prec")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -157,9 +157,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_gru_pack_weights.argtypes = [vp, vp, vp, i, i, vp, vp]
     lib.corr_gru_workspace.argtypes, lib.corr_gru_workspace.restype = [i, i, i, i], sz
     lib.corr_gru_half_step.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.corr_gru_half_step_prec.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, sz, vp, i, vp]
     lib.corr_conv_weights_bytes.argtypes, lib.corr_conv_weights_bytes.restype = [i, i], sz
     lib.corr_conv_pack_weights.argtypes = [vp, i, i, vp, vp]
     lib.corr_conv_forward.argtypes = [vp, i, vp, i, i, i, i, vp, vp, i, i, vp, i, i, vp]
+    lib.corr_conv_forward_prec.argtypes = [vp, i, vp, i, i, i, i, vp, vp, i, i, vp, i, i, i, vp]
     lib.corr_enc_stats_bytes.argtypes, lib.corr_enc_stats_bytes.restype = [i, i, i, i], sz
     lib.corr_enc_conv_forward.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, sz, vp]
     lib.corr_enc_norm_finalize.argtypes = [vp, i, i, i, i, ctypes.c_float, vp, vp, vp]
@@ -180,6 +182,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_flow_head_weights_bytes.argtypes, lib.corr_flow_head_weights_bytes.restype = [], sz
     lib.corr_flow_head_pack_weights.argtypes = [vp, vp, vp]
     lib.corr_flow_head_forward.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    for f in ("corr_gru_half_step_prec", "corr_conv_forward_prec"):
+        getattr(lib, f).restype = i
     for f in ("corr_ondemand_lookup_conv", "corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
               "corr_flow_head_forward", "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
               "corr_enc_join_affine", "corr_mask_upsample_pack_weights", "corr_mask_upsample_forward", "corr_enc_conv_forward", "corr_enc_norm_finalize", "corr_enc_join", "corr_conv_pack_weights", "corr_conv_forward", "corr_gru_pack_weights", "corr_gru_half_step", "corr_ondemand_backward", "corr_ondemand_prepare", "corr_ondemand_lookup", "corr_build_region", "corr_build", "corr_lookup", "corr_lookup_bwd", "corr_pool_bwd", "corr_build_bwd",
@@ -749,9 +753,10 @@ def gru_pack_weights(wz, wr, wq):
                          (hidden, C - hidden), f"hidden = {hidden}, C = {C}")
 
 
-def gru_half_step(h, x, direction, packed, bz, br, bq, workspace=None):
-    """corr_gru_half_step: h [B, hidden, H, W], x [B, input, H, W] -> the new h (allocated here).
-    direction 0 = the 1x5 gates, 1 = the 5x1 ones; packed from gru_pack_weights."""
+def gru_half_step(h, x, direction, packed, bz, br, bq, workspace=None, precision=0):
+    """corr_gru_half_step_prec: h [B, hidden, H, W], x [B, input, H, W] -> the new h (allocated
+    here).  direction 0 = the 1x5 gates, 1 = the 5x1 ones; packed from gru_pack_weights; precision
+    a CORR_PREC_* value (precision.py; 0 = bf16x6 is corr_gru_half_step itself, bit for bit)."""
     B, hidden, H, W = h.shape
     if x.dim() != 4 or x.shape[0] != B or tuple(x.shape[2:]) != (H, W):
         raise ValueError(f"x {tuple(x.shape)} does not match h {tuple(h.shape)}")
@@ -762,9 +767,9 @@ def gru_half_step(h, x, direction, packed, bz, br, bq, workspace=None):
         workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=h.device)
     out = torch.empty_like(h)
     with torch.cuda.device(h.device):
-        _check(lib.corr_gru_half_step(hp, xp, B, hidden, x.shape[1], H, W, direction, pk, _dev(bz, "bz"),
-                                      _dev(br, "br"), _dev(bq, "bq"), _dev(workspace, "workspace"),
-                                      workspace.numel() * 4, out.data_ptr(), _stream(h)))
+        _check(lib.corr_gru_half_step_prec(hp, xp, B, hidden, x.shape[1], H, W, direction, pk, _dev(bz, "bz"),
+                                           _dev(br, "br"), _dev(bq, "bq"), _dev(workspace, "workspace"),
+                                           workspace.numel() * 4, out.data_ptr(), int(precision), _stream(h)))
     return out
 
 
@@ -788,10 +793,12 @@ def conv_pack_weights(weights):
                          f"cout = {cout}, cin = {cin}")
 
 
-def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0):
-    """corr_conv_forward: the 3x3 convolution (+ bias, + ReLU) of cat([in_a, in_b]) (in_b may be
-    None) with the pack of conv_pack_weights, written into channels out_offset .. + cout - 1 of
-    `out` [B, out_channels, H, W] (allocated as [B, cout, H, W] when None).  Returns `out`."""
+def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0, precision=0):
+    """corr_conv_forward_prec: the 3x3 convolution (+ bias, + ReLU) of cat([in_a, in_b]) (in_b may
+    be None) with the pack of conv_pack_weights, written into channels out_offset .. + cout - 1 of
+    `out` [B, out_channels, H, W] (allocated as [B, cout, H, W] when None).  Returns `out`.
+    precision is a CORR_PREC_* value (precision.py; 0 = bf16x6 is corr_conv_forward itself, bit for
+    bit)."""
     ap = _dev(in_a, "in_a")
     if in_a.dim() != 4:
         raise ValueError(f"in_a must be [B, ca, H, W] (got {tuple(in_a.shape)})")
@@ -816,8 +823,8 @@ def conv_forward(in_a, in_b, packed, bias, cout, relu, out=None, out_offset=0):
         out = torch.empty((B, cout, H, W), dtype=torch.float32, device=in_a.device)
     op = _window_arg(out, "out", B, H, W, out_offset, cout, in_a.device)
     with torch.cuda.device(in_a.device):
-        _check(lib.corr_conv_forward(ap, ca, bp, cb, B, H, W, pk, biasp, cout, int(bool(relu)), op, out.shape[1],
-                                     out_offset, _stream(in_a)))
+        _check(lib.corr_conv_forward_prec(ap, ca, bp, cb, B, H, W, pk, biasp, cout, int(bool(relu)), op,
+                                          out.shape[1], out_offset, int(precision), _stream(in_a)))
     return out
 
 

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from .corr import CorrBlock
 from .ondemand import OnDemandConvCorrBlock, OnDemandCorrBlock
+from .precision import DEFAULT as _PRECISION, resolve as _resolve_precision
 from .utils import coords_grid
 
 
@@ -174,6 +175,9 @@ class SepConvGRU(nn.Module):
     # HIP launches on the bf16 MFMA, gru.py) instead of the torch / MIOpen chain below.  Default
     # off (DESIGN §14 has the measurements); training always runs the torch code.
     fused = os.environ.get("ERAFT_AMD_FUSE_GRU", "0") == "1"
+    # The fused half steps' precision mode (precision.py); ERAFT sets it on its instances.  The
+    # torch path and training are fp32 and ignore it.
+    precision = _PRECISION
 
     def __init__(self, hidden_dim=128, input_dim=192 + 128):
         super().__init__()
@@ -230,6 +234,9 @@ class BasicUpdateBlock(nn.Module):
     # corr_flow_head_forward launches.  Default off (DESIGN §15 and §19 have the measurements);
     # training always runs the torch code.
     fused = os.environ.get("ERAFT_AMD_FUSE_UPDATE", "0") == "1"
+    # The fused 3x3 convolutions' precision mode (precision.py); ERAFT sets it on its instances.
+    # The torch path and training are fp32 and ignore it.
+    precision = _PRECISION
 
     def __init__(self, corr_levels=4, corr_radius=4, hidden_dim=128):
         super().__init__()
@@ -349,6 +356,9 @@ class ERAFT(nn.Module):
     # HBM, no torch convc1); under autograd it is the unfused composition.  Default off (DESIGN §21
     # has the measurements).
     fuse_ondemand_conv = os.environ.get("ERAFT_AMD_ONDEMAND_FUSE_CONV", "0") == "1"
+    # The precision mode of the GRU and the update block's 3x3 convolutions ("bf16x6", "bf16x3" or
+    # "bf16": precision.py); an instance takes it from its config (below).
+    precision = _PRECISION
 
     def __init__(self, config, n_first_channels):
         super().__init__()
@@ -368,6 +378,12 @@ class ERAFT(nn.Module):
         self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn="batch", dropout=0,
                                  n_first_channels=n_first_channels)
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=hdim)
+        # The reference's switch: config key `mixed_precision` (absent / False: "bf16x6", every
+        # product exact as before; True: "bf16x3"; or a mode's name), ERAFT_AMD_PRECISION=<name>
+        # overrides it.  It acts only where the fused kernels run (ERAFT_AMD_FUSE_GRU=1 /
+        # ERAFT_AMD_FUSE_UPDATE=1 at inference); the torch paths and training stay fp32.
+        self.precision = _resolve_precision(config)
+        self.update_block.precision = self.update_block.gru.precision = self.precision
 
     def freeze_bn(self):
         for m in self.modules():

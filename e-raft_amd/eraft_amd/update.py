@@ -6,6 +6,12 @@ convolution of the flow (convf1) as a corr_flow_enc_forward launch that also dro
 the GRU input, and the flow head's second convolution as a corr_flow_head_forward launch that also
 updates the coordinates (csrc/corr_flow.hip).  Inference only: there is no backward, so
 model.BasicUpdateBlock takes this path only when autograd is not recording.
+
+The module's `precision` ("bf16x6", the class default, "bf16x3" or "bf16": precision.py) selects the
+pieces of the split that the five corr_conv_forward launches keep (convc2, convf2, conv,
+flow_head.conv1 and mask[0]); the GRU follows its own module's.  convf1 and the flow head's second
+convolution, through which the flow enters and the flow delta leaves, stay bf16x6, and the torch
+path ignores the mode.
 """
 from __future__ import annotations
 
@@ -14,6 +20,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._cache import cached
+from .precision import DEFAULT, code
 
 # Which convolutions take the HIP kernel under the switch (each is judged on its
 # own against the torch ops it replaces, at DSEC and at b8).  One that is False runs on MIOpen and
@@ -41,12 +48,13 @@ def _flow_head_pack(conv):
                   lambda: (_lib.flow_head_pack_weights(conv.weight), conv.bias.detach().float().contiguous().clone()))
 
 
-def _conv(name, convs, x, out, off):
-    """relu(conv(x)) of the stacked `convs` into channels off .. of `out`."""
+def _conv(name, convs, x, out, off, precision=0):
+    """relu(conv(x)) of the stacked `convs` into channels off .. of `out`; `precision` (a
+    CORR_PREC_* value) acts on the kernel only."""
     cout = sum(c.out_channels for c in convs)
     if USE_KERNEL[name]:
         packed, bias = _conv_pack(convs)
-        _lib.conv_forward(x, None, packed, bias, cout, True, out=out, out_offset=off)
+        _lib.conv_forward(x, None, packed, bias, cout, True, out=out, out_offset=off, precision=precision)
     else:
         for c in convs:
             out[:, off:off + c.out_channels].copy_(F.relu(c(x)))
@@ -99,6 +107,7 @@ def update_block(module, net, inp, corr, flow, fused=False, defer_mask=False, wo
     if coords0 is not None and coords1 is None:
         raise ValueError("coords0 needs coords1")
     enc = module.encoder
+    prec = code(getattr(module, "precision", DEFAULT))
     net, inp, corr, flow = (t.detach() for t in (net, inp, corr, flow))
     ws = workspace if workspace is not None else UpdateWorkspace(inp)
     if tuple(ws.x.shape) != (net.shape[0], 256, *net.shape[2:]) or ws.x.device != net.device:
@@ -106,7 +115,7 @@ def update_block(module, net, inp, corr, flow, fused=False, defer_mask=False, wo
                          f"on {net.device}")
     c1 = (corr if fused else F.relu(enc.convc1(corr))).contiguous()
     cf, x, hd = ws.cf, ws.x, ws.hd
-    _conv("convc2", (enc.convc2,), c1, cf, 0)
+    _conv("convc2", (enc.convc2,), c1, cf, 0, prec)
     flow = flow.contiguous()
     if USE_KERNEL["convf1"]:
         packed, bias = _flow_enc_pack(enc.convf1)
@@ -114,10 +123,10 @@ def update_block(module, net, inp, corr, flow, fused=False, defer_mask=False, wo
     else:
         ws.f1.copy_(F.relu(enc.convf1(flow)))
         x[:, 254:].copy_(flow)
-    _conv("convf2", (enc.convf2,), ws.f1, cf, 192)
-    _conv("conv", (enc.conv,), cf, x, 128)
+    _conv("convf2", (enc.convf2,), ws.f1, cf, 192, prec)
+    _conv("conv", (enc.conv,), cf, x, 128, prec)
     net = module.gru(net.contiguous(), x)
-    _conv("heads", (module.flow_head.conv1, module.mask[0]), net.contiguous(), hd, 0)
+    _conv("heads", (module.flow_head.conv1, module.mask[0]), net.contiguous(), hd, 0, prec)
     head2 = module.flow_head.conv2
     coords_out = flow_out = None
     if coords1 is not None:

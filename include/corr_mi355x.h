@@ -538,6 +538,29 @@ int corr_gru_half_step(const float *h, const float *x, int B, int hidden, int in
                        size_t workspace_bytes, float *h_out, void *stream);
 
 /*
+ * Reduced precision for the per-iteration kernels (opt-in; the counterpart of the reference's
+ * mixed_precision, model/eraft.py:31,102-133).  A mode keeps fewer of the pieces of the exact
+ * three-piece bf16 split x = hi + mid + lo of BOTH operands (the split's guards included, so an
+ * infinite operand still splits as (inf, 0, 0) and the non-finite pattern stays fp32's) and
+ * multiplies only the products among the kept pieces, in this order per K step:
+ *   CORR_PREC_BF16X6  hi, mid, lo  the six products of corr_gru_half_step / corr_conv_forward
+ *   CORR_PREC_BF16X3  hi, mid      acs += wm xh; acs += wh xm; acc += wh xh   (joined at the end)
+ *   CORR_PREC_BF16    hi           acc += wh xh                              (one accumulator)
+ * The accumulators are fp32 in every mode and the K order is unchanged.  With S = sum |w| |x|
+ * over an output's products, the operand rounding adds at most 2^-16 S (BF16X3) or
+ * (2^-8 + 2^-18) S (BF16) to the fp32 accumulation error.  The packs are the same for every mode.
+ * corr_gru_half_step_prec and corr_conv_forward_prec are corr_gru_half_step and corr_conv_forward
+ * with `precision` (before `stream`); CORR_PREC_BF16X6 is bit-identical to them.  An unknown
+ * precision is CORR_EINVAL, refused before every other check and before any HIP call.
+ */
+#define CORR_PREC_BF16X6 0
+#define CORR_PREC_BF16X3 1
+#define CORR_PREC_BF16 2
+int corr_gru_half_step_prec(const float *h, const float *x, int B, int hidden, int input, int H, int W, int dir,
+                            const void *packed, const float *bz, const float *br, const float *bq, void *workspace,
+                            size_t workspace_bytes, float *h_out, int precision, void *stream);
+
+/*
  * A 3x3 convolution (stride 1, zero padding 1) with bias and an optional ReLU, inference only
  * (no backward): the update block's convc2, convf2, conv and the first convolutions of the flow
  * head and the mask head (model/update.py:63-107).
@@ -575,6 +598,10 @@ int corr_conv_pack_weights(const float *w, int cout, int cin, void *packed, void
 int corr_conv_forward(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
                       const void *packed, const float *bias, int cout, int relu, float *out,
                       int out_channels, int out_offset, void *stream);
+/* corr_conv_forward in a CORR_PREC_* mode (see corr_gru_half_step_prec). */
+int corr_conv_forward_prec(const float *in_a, int ca, const float *in_b, int cb, int B, int H, int W,
+                           const void *packed, const float *bias, int cout, int relu, float *out,
+                           int out_channels, int out_offset, int precision, void *stream);
 
 /*
  * The encoders' residual stages (model/extractor.py: ResidualBlock with norm_fn "instance" or,

@@ -2,6 +2,11 @@
 Every variant is captured as one HIP graph and replayed; the variants of a measurement are
 alternated in ONE process on the same inputs, so box-to-box spread drops out.
     python tools/bench_update.py [--sizes dsec,b8,hires1920] [--trials 5] [--json profiles/update_bench.json]
+                                 [--precision bf16x3,bf16]
+--precision adds, for each named reduced mode (eraft_amd/precision.py), the variant kernel_<mode> to
+the four corr_conv_forward launches of (a) and iter_tail_<mode> (the block and its GRU in that mode;
+the GRU is fused only under ERAFT_AMD_FUSE_GRU=1) to (b), alternated with the others in the same
+windows, and their ratios to "kernel" and "iter_tail" (bf16x6).
 Per size:
   (a) each of the four launches (convc2, convf2, conv, the stacked heads) against the torch ops it
       replaces: conv + bias + ReLU and the cat it removes (convf2 carries cat([c, f]); conv carries
@@ -32,6 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "e-raft_amd"))
 from eraft_amd import _lib, update  # noqa: E402
 from eraft_amd.model import BasicUpdateBlock  # noqa: E402
+from eraft_amd.precision import code  # noqa: E402
 
 # name: (B, H, W)
 SIZES = {"dsec": (1, 60, 80), "b8": (8, 36, 48), "hires1920": (1, 160, 240)}
@@ -74,7 +80,7 @@ def alternate(graphs, trials, steps):
     return res
 
 
-def bench_size(name, trials, dev):
+def bench_size(name, trials, dev, modes=()):
     B, H, W = SIZES[name]
     gen = torch.Generator(device=dev).manual_seed(1234)
     torch.manual_seed(1234)
@@ -90,15 +96,21 @@ def bench_size(name, trials, dev):
     buf = lambda ch: torch.empty(B, ch, H, W, device=dev)
     cfb, xb, hdb = buf(256), buf(256), buf(512)
 
-    def kernel_conv(convs, x, out, off):
+    def kernel_conv(convs, x, out, off, prec=0):
         packed, bias = update._conv_pack(convs)
         return _lib.conv_forward(x, None, packed, bias, sum(k.out_channels for k in convs), True, out=out,
-                                 out_offset=off)
+                                 out_offset=off, precision=prec)
 
-    def fused_conv():
+    def fused_conv(prec=0):
         xb[:, :128].copy_(inp)
         xb[:, 254:].copy_(flow)
-        return kernel_conv((enc.conv,), cf, xb, 128)
+        return kernel_conv((enc.conv,), cf, xb, 128, prec)
+
+    # the same four launches in a reduced mode (into the same buffers: the variants run one at a time)
+    in_mode = {"convc2": lambda p: kernel_conv((enc.convc2,), c1, cfb, 0, p),
+               "convf2": lambda p: kernel_conv((enc.convf2,), f1, cfb, 192, p),
+               "conv": fused_conv,
+               "heads": lambda p: kernel_conv((m.flow_head.conv1, m.mask[0]), net, hdb, 0, p)}
 
     heads = (m.flow_head.conv1, m.mask[0])
     pairs = {
@@ -118,7 +130,12 @@ def bench_size(name, trials, dev):
     for lname, (torch_fn, kernel_fn, window) in pairs.items():
         gt, ot, kt = capture(torch_fn, stream)
         gk, ok, kk = capture(kernel_fn, stream)
-        r = alternate({"torch": gt, "kernel": gk}, trials, steps)
+        ok = ok.clone()  # the reduced modes below write into the same buffer
+        gm, om = {}, {}
+        for p in modes:  # each mode's output is copied before the next mode's warm-up overwrites the buffer
+            gm[f"kernel_{p}"] = capture(lambda p=p: in_mode[lname](code(p)), stream)
+            om[f"kernel_{p}"] = window(gm[f"kernel_{p}"][1]).clone()
+        r = alternate({"torch": gt, "kernel": gk, **{n: cp[0] for n, cp in gm.items()}}, trials, steps)
         ot = torch.cat(ot, dim=1) if isinstance(ot, tuple) else ot
         ot = {"convc2": ot, "convf2": ot[:, 192:], "conv": ot[:, 128:254], "heads": ot}[lname]
         convs = {"convc2": (enc.convc2,), "convf2": (enc.convf2,), "conv": (enc.conv,), "heads": heads}[lname]
@@ -129,8 +146,11 @@ def bench_size(name, trials, dev):
         r["kernel"]["rel_err_vs_fp64"] = norm_rel(window(ok).cpu(), ref)
         r["torch"]["rel_err_vs_fp64"] = norm_rel(ot.cpu(), ref)
         r["kernel_over_torch"] = round(r["kernel"]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
+        for n in gm:
+            r[n]["rel_err_vs_fp64"] = norm_rel(om[n].cpu(), ref)
+            r[f"{n}_over_kernel"] = round(r[n]["call_ms_median"] / r["kernel"]["call_ms_median"], 3)
         res["launches"][lname] = r
-        del gt, gk, kt, kk
+        del gt, gk, kt, kk, gm
 
     # (a) continued: the tail's two launches (corr_flow.hip), each against the torch ops it replaces
     hd = torch.relu(rnd(512))
@@ -194,17 +214,23 @@ def bench_size(name, trials, dev):
         c = coords1 + out[2]
         return out + (c, c - coords0)
 
+    def iter_tail():
+        return m(net, inp, c1, flow, True, workspace=ws, coords1=coords1, coords0=coords0)
+
     graphs, outs, keep = {}, {}, []
-    for vname, on, tab, fn in (
-            ("torch", False, table, None), ("all", True, dict.fromkeys(table, True), None), ("fused", True, table, None),
-            ("iter_torch", False, table, plain_iter), ("iter_no_tail", True, no_tail, plain_iter),
-            ("iter_tail", True, table, lambda: m(net, inp, c1, flow, True, workspace=ws, coords1=coords1,
-                                                 coords0=coords0))):
+    for vname, on, tab, fn, prec in [
+            ("torch", False, table, None, "bf16x6"), ("all", True, dict.fromkeys(table, True), None, "bf16x6"),
+            ("fused", True, table, None, "bf16x6"), ("iter_torch", False, table, plain_iter, "bf16x6"),
+            ("iter_no_tail", True, no_tail, plain_iter, "bf16x6"), ("iter_tail", True, table, iter_tail, "bf16x6"),
+            *((f"iter_tail_{p}", True, table, iter_tail, p) for p in modes)]:
         BasicUpdateBlock.fused = on
+        m.precision = m.gru.precision = prec
         update.USE_KERNEL.update(tab)
-        graphs[vname], outs[vname], k = capture(fn or (lambda: m(net, inp, c1, flow, True)), stream)
+        graphs[vname], out, k = capture(fn or (lambda: m(net, inp, c1, flow, True)), stream)
+        outs[vname] = tuple(None if t is None else t.clone() for t in out)  # iter_tail's variants share the workspace
         keep.append(k)
     BasicUpdateBlock.fused = False
+    m.precision = m.gru.precision = "bf16x6"
     update.USE_KERNEL.update(table)
     with torch.no_grad():
         ref = copy.deepcopy(m).cpu().double()(*(t.cpu().double() for t in (net, inp, c1, flow)), True)
@@ -218,6 +244,8 @@ def bench_size(name, trials, dev):
     r["all_over_torch"] = round(r["all"]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
     r["iter_tail_over_iter_no_tail"] = round(r["iter_tail"]["call_ms_median"] / r["iter_no_tail"]["call_ms_median"], 3)
     r["iter_tail_over_iter_torch"] = round(r["iter_tail"]["call_ms_median"] / r["iter_torch"]["call_ms_median"], 3)
+    for p in modes:
+        r[f"iter_tail_{p}_over_iter_tail"] = round(r[f"iter_tail_{p}"]["call_ms_median"] / r["iter_tail"]["call_ms_median"], 3)
     res["block"] = r
     del graphs, keep
     torch.cuda.empty_cache()
@@ -229,7 +257,12 @@ def main():
     ap.add_argument("--sizes", default="dsec,b8,hires1920")
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--precision", default="", help="reduced modes to time beside bf16x6, e.g. bf16x3,bf16")
     a = ap.parse_args()
+    modes = tuple(p for p in a.precision.split(",") if p)
+    for p in modes:
+        if code(p) == 0:
+            sys.exit("--precision names the reduced modes; bf16x6 is the variants 'kernel' and 'iter_tail'")
     if not torch.cuda.is_available():
         sys.exit("bench_update needs an MI355X (no CPU fallback)")
     if a.trials < 5:
@@ -238,7 +271,7 @@ def main():
     doc = {"device": torch.cuda.get_device_name(0),
            "call": "one HIP graph per variant, variants alternated; launches: kernel vs the torch ops it replaces; "
                    "block: BasicUpdateBlock.forward on relu(convc1(lookup))",
-           "sizes": {n: bench_size(n, a.trials, dev) for n in a.sizes.split(",")}}
+           "sizes": {n: bench_size(n, a.trials, dev, modes) for n in a.sizes.split(",")}}
     text = json.dumps(doc, indent=1)
     print(text)
     if a.json:
