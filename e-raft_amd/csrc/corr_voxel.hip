@@ -6,6 +6,12 @@
 //   t_n = ((C-1)(t - t_0)) / (t_{M-1} - t_0); corners (x_l, y_l) in {x0, x0+1} x {y0, y0+1}
 //   (x0 = trunc x), t_l = trunc t_n; weight ((2p-1)(1-|x_l-x|))(1-|y_l-y|))(1-|t_l-t_n|);
 //   in-bounds corners accumulate at H*W*t_l + W*y_l + x_l.
+// trunc is the reference's Tensor.int() on its x86 CPU: toward zero (so x in (-1, 0) makes the
+// corner 0, with a negative weight on corner 1), and INT_MIN for NaN, +-inf and values outside
+// int32, which no bounds test admits: an event with such a coordinate votes nowhere.  A window
+// with t_{M-1} == t_0 (one event, equal stamps) has t_n = NaN or +-inf throughout and gives the
+// all-zero grid, as the reference does; nothing else about x, y, t, p is assumed (stamps may be
+// unsorted or outside [0, 1], p any float, NaN included: the weight carries it into the cell).
 // The reference accumulates with put_(accumulate=True) — single-threaded (main.py:2-5 pins one
 // thread) that is a sequential pass per corner in event order.  As in corr_splat.hip the
 // accumulation is made deterministic and order-exact without float atomics: count entries per
@@ -52,13 +58,23 @@ struct VoxTArgs {
     __device__ __forceinline__ VoxEntry entry(int e) const;
 };
 
+// Tensor.int() as the reference's x86 CPU does it (dsec_utils.py:35-37): truncation toward zero
+// inside [-2^31, 2^31), INT_MIN for NaN, +-inf and everything else, which then fails the >= 0
+// tests below.  A bare (int) cast is v_cvt_i32_f32 here: NaN -> 0 (admitted, with a NaN weight)
+// and saturation to INT_MAX (x0 + 1 overflows).  NaN fails both comparisons.
+__device__ __forceinline__ int vox_trunc_i32(float v) {
+    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (-2147483647 - 1);
+}
+
 __device__ __forceinline__ VoxEntry VoxArgs::entry(int e) const {
     const VoxArgs &a = *this;
     const int corner = e / a.M, i = e - corner * a.M;
     const float t0 = a.t[0], dt = __fsub_rn(a.t[a.M - 1], t0);
     const float tn = __fdiv_rn(__fmul_rn((float)(a.C - 1), __fsub_rn(a.t[i], t0)), dt);
     const float xf = a.x[i], yf = a.y[i];
-    const int xl = (int)xf + (corner >> 1), yl = (int)yf + (corner & 1), tl = (int)tn;
+    // x0 <= 2^31 - 128 (the largest float below 2^31) and INT_MIN + 1 < 0: x0 + 1 cannot overflow
+    const int xl = vox_trunc_i32(xf) + (corner >> 1), yl = vox_trunc_i32(yf) + (corner & 1);
+    const int tl = vox_trunc_i32(tn);
     VoxEntry r;
     const bool in = xl < a.W && xl >= 0 && yl < a.H && yl >= 0 && tl >= 0 && tl < a.C;
     r.cell = in ? (tl * a.H + yl) * a.W + xl : -1;

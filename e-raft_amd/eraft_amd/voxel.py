@@ -10,6 +10,14 @@ Events are float32 tensors on an MI355X (x, y rectified pixel coordinates, t nor
 [bins, height, width] float32 grid, computed by corr_voxel_grid (csrc/corr_voxel.hip).  No
 CPU fallback: CPU tensors raise.
 
+Inputs outside that description get the answer the reference gives on its CPU.  x, y and the
+normalised stamp are truncated as Tensor.int() does there: toward zero, and to INT_MIN (a corner
+no bounds test admits) for NaN, +-inf and values outside int32, so such an event votes nowhere.
+A window whose last stamp equals its first (one event, equal stamps, the loader's t = [NaN])
+therefore gives the all-zero grid, normalised or not.  Stamps may be unsorted or outside [0, 1],
+p may be any float (a NaN polarity makes its cells NaN, and normalisation then makes every
+nonzero cell NaN).  An empty window, which the reference cannot take, gives zeros.
+
 MVSEC: drop-in for utils/transformers.py:18-126 EventSequenceToVoxelGrid_Pytorch.
 
     voxel = EventSequenceToVoxelGrid(num_bins=5, normalize=True)   # loader_mvsec_flow.py:35

@@ -315,7 +315,16 @@ void oracle_forward_splat(const float *flow, int B, int H, int W, float *out) {
  *   normalize (:54-62): over the nonzero cells, v = (v - mean) / std (unbiased std; when
  *   std is not > 0: v - mean).  mean and std are accumulated in fp64 here and rounded to
  *   fp32 (the reference's fp32 reduction order is ATen's: tolerance-level for this step).
+ *   Tensor.int() (:35-37) on the reference's x86 CPU turns NaN, +-inf and every value outside
+ *   int32 into INT_MIN, which fails the >= 0 tests: such an event (or, when t[M-1] == t[0]
+ *   makes every t_n NaN or +-inf, the whole window) votes nowhere.  A C cast of those values
+ *   is undefined, so trunc_i32 states the rule with comparisons.
  */
+static int32_t trunc_i32(float v) {
+    /* NaN fails both comparisons; [-2^31, 2^31) truncates toward zero */
+    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : INT32_MIN;
+}
+
 void oracle_voxel_grid(const float *x, const float *y, const float *t, const float *p, long M, int C, int H,
                        int W, int normalize, float *out) {
     const long CHW = (long)C * H * W;
@@ -326,7 +335,8 @@ void oracle_voxel_grid(const float *x, const float *y, const float *t, const flo
         for (int yi = 0; yi < 2; ++yi)
             for (long e = 0; e < M; ++e) {
                 const float tn = ((float)(C - 1) * (t[e] - t0)) / dt;
-                const int xl = (int)x[e] + xi, yl = (int)y[e] + yi, tl = (int)tn;
+                /* the largest float below 2^31 is 2^31 - 128 and INT32_MIN + 1 is negative: no overflow */
+                const int xl = trunc_i32(x[e]) + xi, yl = trunc_i32(y[e]) + yi, tl = trunc_i32(tn);
                 if (!(xl < W && xl >= 0 && yl < H && yl >= 0 && tl >= 0 && tl < C)) continue;
                 const float value = 2.0f * p[e] - 1.0f;
                 const float w = value * (1.0f - fabsf((float)xl - x[e])) * (1.0f - fabsf((float)yl - y[e])) *

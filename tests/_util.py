@@ -40,6 +40,24 @@ def bit_equal(a, b):
     return np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
 
 
+def voxel_edge_cases(g, kind):
+    """Case names of g_voxel_edges.npz: kind "d" (VoxelGrid) or "m" (EventSequenceToVoxelGrid)."""
+    pre = kind + "_ev_"
+    return sorted(k[len(pre):] for k in g if k.startswith(pre))
+
+
+def same_zero_nan_pattern(a, b):
+    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a == 0, b == 0)
+
+
+def voxel_norm_within_bar(n, ref):
+    """The suite's bar for a normalised voxel grid, 1e-6 of max|v|, over the finite cells, and
+    the same zero and NaN pattern."""
+    fin = np.isfinite(ref)
+    return same_zero_nan_pattern(n, ref) and \
+        np.abs(n[fin] - ref[fin]).max(initial=0.0) <= 1e-6 * np.abs(ref[fin]).max(initial=0.0)
+
+
 def tiled_levels(B, H, W, L, device, fill=None, NQ=None):
     """Separate tiled level tensors [B*NQ, map_floats(H_l, W_l)] (the library's value pyramid,
     include/corr_mi355x.h), optionally filled with `fill`."""

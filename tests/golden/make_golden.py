@@ -212,7 +212,124 @@ def case_voxel_mvsec(name, seed):
     save(name, **out)
 
 
+def voxel_edge_events():
+    """The inputs of case_voxel_edges: {name: (ev [4, M] float32 rows x, y, t, p, (C, H, W))}
+    for VoxelGrid and {name: (ev [M, 4] float64 rows t, x, y, p, (C, H, W))} for
+    EventSequenceToVoxelGrid_Pytorch.  Written out by hand: every value is the point."""
+    C, H, W = 5, 6, 8
+    nan, inf = np.nan, np.inf
+    d, m = {}, {}
+
+    def dsec(name, rows):
+        d[name] = (np.ascontiguousarray(np.array(rows, np.float32).T), (C, H, W))
+
+    def mvsec(name, rows):
+        m[name] = (np.ascontiguousarray(np.array(rows, np.float64)), (C, H, W))
+
+    # degenerate windows: t[M-1] == t[0] -> t_n = 0/0 (or x/0) for every event -> Tensor.int()
+    # gives INT_MIN -> no corner passes the mask -> the grid stays zero
+    dsec("single", [(2.5, 3.25, 0.0, 1)])
+    dsec("single_nan_t", [(2.5, 3.25, nan, 1)])            # what loader_dsec.py:246-247 hands over
+    dsec("equal_stamps", [(2.5, 3.25, 0.5, 1), (1.0, 2.0, 0.5, 0), (6.75, 0.5, 0.5, 1), (2.5, 3.25, 0.5, 0)])
+    dsec("ends_equal", [(2.5, 3.25, 0.0, 1), (1.0, 2.0, 0.5, 0), (6.75, 0.5, 0.25, 1), (2.5, 3.25, 0.0, 0)])
+    dsec("ends_equal_neg", [(2.5, 3.25, 0.5, 1), (1.0, 2.0, 0.75, 0), (6.75, 0.5, 0.25, 1), (2.5, 3.25, 0.5, 0)])
+
+    # NaN / inf / beyond-int32 coordinates between ordinary events that vote into cells (0, 0),
+    # (0, 1), (1, 0), (1, 1) of bin 0: an admitted event would change a sum or its order
+    big = 2147483520.0                                      # the largest float32 below 2^31
+    odd = [(nan, 0.5), (0.25, nan), (nan, nan), (inf, 0.5), (-inf, 0.5), (3e9, 0.5), (-3e9, 0.5), (big, 0.5),
+           (0.25, inf), (0.25, -inf), (0.25, 3e9), (0.25, -3e9), (0.25, big), (-big, 0.5), (0.25, -big)]
+    rows = []
+    for k, (ox, oy) in enumerate(odd):
+        rows.append((0.125 + 0.0625 * (k % 7), 0.875 - 0.09375 * (k % 5), 0.0, k % 3 != 0))
+        rows.append((ox, oy, 0.0, k % 2))
+    rows.append((0.3125, 0.4375, 0.0, 1))
+    rows.append((5.5, 4.5, 0.0, 1))                         # the last stamp: t_n = C - 1
+    ts = np.concatenate([np.arange(len(rows) - 1) * np.float32(1 / 128), [1.0]])  # ascending, bin 0 but the last
+    dsec("nan_coords", [(x, y, t, p) for (x, y, _, p), t in zip(rows, ts)])
+
+    dsec("outside", [
+        (-0.5, -0.25, 0.0, 1),       # trunc toward zero: corner (0, 0), negative weights on column / row 1
+        (0.5, 0.25, 0.125, 0),
+        (-1.5, 2.5, 0.25, 1),        # corner -1 dropped, corner 0 weighs -0.5
+        (W - 0.5, 2.25, 0.375, 1),   # corner W dropped
+        (float(W), 1.5, 0.5, 0),     # both corners out
+        (3.5, H - 0.5, 0.625, 1),
+        (2.5, float(H), 0.75, 0),
+        (-1.0, 3.0, 0.8125, 1),      # corner 0 with weight exactly 0
+        (0.5, 2.5, 0.875, 1),
+        (7.25, 5.5, 1.0, 0)])
+
+    # unsorted stamps: t[0] = 2, t[M-1] = 6, span 4 = C - 1, so t_n = t - 2
+    dsec("t_outside", [
+        (2.5, 3.25, 2.0, 1),         # t_n 0
+        (2.5, 3.25, 1.5, 0),         # -0.5: truncates to bin 0, weight 0.5
+        (2.5, 3.25, 0.5, 1),         # -1.5: bin -1, dropped
+        (2.5, 3.25, 6.5, 1),         # C - 0.5: bin C - 1, weight 0.5
+        (2.5, 3.25, 9.0, 0),         # C + 2: dropped
+        (1.75, 4.5, 3.25, 0),        # 1.25
+        (2.5, 3.25, 6.0, 1)])        # exactly C - 1, weight 1
+
+    polarity = [(1.5, 2.5, 0.0, 0), (1.5, 2.5, 0.125, 1), (1.25, 2.75, 0.25, 0.5), (4.5, 1.5, 0.5, 2),
+                (4.25, 1.25, 0.5625, -1), (6.5, 4.5, 0.75, nan),   # a pixel no other event touches
+                (1.5, 2.5, 1.0, 1)]
+    dsec("polarity", polarity)
+    dsec("nan_cell", polarity)                              # the same events, read for the normalised grid
+
+    # normalisation rules: integer coordinates, stamps on exact bins -> every vote is +-1 (or +-0)
+    dsec("one_cell", [(2, 3, 0.0, 1), (-5, 0, 1.0, 1)])    # std of one value is NaN -> v - mean = 0
+    dsec("equal_cells", [(2, 3, 0.0, 1), (5, 1, 1.0, 1)])  # std 0 -> v - mean = 0
+    dsec("cancelled", [(1, 1, 0.0, 1), (1, 1, 0.0, 1), (6, 4, 0.25, 1), (5, 5, 0.75, 1), (5, 5, 0.75, 0),
+                       (3, 2, 1.0, 0)])                     # {+2, +1, -1} and a cell that cancels to 0
+
+    mvsec("wrap", [
+        (0.0, 1, 1, 1), (50.0, W + 2, 2, 1),    # x = W + 2 at row 2: two cells into row 3
+        (100.0, 2, 3, 0), (150.0, -1, 3, 1),    # x = -1 at row 3: the last cell of row 2
+        (200.0, 7, 2, 1), (250.0, -0.5, 4, 0),  # x = -0.5 truncates to 0
+        (300.0, 0, 4, 1), (400.0, 3, 5, 1)])
+    mvsec("nan_t", [(0.0, 1, 1, 1), (120.0, 2, 3, 0), (nan, 2, 3, 1), (260.0, 2, 3, 1), (400.0, 3, 5, 0)])
+    mvsec("one_cell", [(100.0, 2, 3, 1), (100.0, 2, 3, 1)])
+    mvsec("equal_cells", [(0.0, 2, 3, 1), (400.0, 5, 1, 1)])
+    mvsec("cancelled", [(0.0, 1, 1, 1), (0.0, 1, 1, 1), (100.0, 6, 4, 1), (300.0, 5, 5, 1), (300.0, 5, 5, 0),
+                        (400.0, 3, 2, 0)])
+    return d, m
+
+
+def case_voxel_edges(name):
+    """Both voxel representations at the edges the bulk fixtures leave out: degenerate time
+    windows, NaN / inf / beyond-int32 coordinates, corners and bins just outside the grid, odd
+    polarities, MVSEC events whose flat index wraps into a neighbouring row, and grids on which
+    each branch of the normalisation is the whole answer.  Only events the reference accepts."""
+    import types
+    from utils.dsec_utils import VoxelGrid
+    from utils.transformers import EventSequenceToVoxelGrid_Pytorch
+    torch.set_num_threads(1)
+    d, m = voxel_edge_events()
+    out = {}
+    for tag, (ev, (C, H, W)) in d.items():
+        evt = {k: torch.from_numpy(ev[i].copy()) for i, k in enumerate("xytp")}
+        out[f"d_ev_{tag}"] = ev
+        out[f"d_meta_{tag}"] = np.array([ev.shape[1], C, H, W], np.int64)
+        out[f"d_raw_{tag}"] = VoxelGrid((C, H, W), normalize=False).convert(evt).numpy()
+        out[f"d_norm_{tag}"] = VoxelGrid((C, H, W), normalize=True).convert(evt).numpy()
+    # observed with Tensor.int() on an x86 CPU (NaN, +-inf -> INT_MIN): if a torch build converts
+    # differently these grids are not zero, and the fixture must not be made silently
+    for tag in ("single", "single_nan_t", "equal_stamps", "ends_equal", "ends_equal_neg"):
+        assert not out[f"d_raw_{tag}"].any() and not out[f"d_norm_{tag}"].any(), tag
+    for tag, (ev, (C, H, W)) in m.items():
+        seq = types.SimpleNamespace(features=ev, image_width=W, image_height=H)
+        out[f"m_ev_{tag}"] = ev
+        out[f"m_meta_{tag}"] = np.array([ev.shape[0], C, H, W], np.int64)
+        for norm, key in ((False, "raw"), (True, "norm")):
+            conv = EventSequenceToVoxelGrid_Pytorch(C, gpu=False, normalize=norm, forkserver=False)
+            out[f"m_{key}_{tag}"] = conv(seq).numpy()
+    save(name, **out)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "voxel_edges":
+        case_voxel_edges("g_voxel_edges")
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "voxel_mvsec":
         case_voxel_mvsec("g_voxel_mvsec", 51)
         sys.exit(0)

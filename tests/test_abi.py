@@ -232,3 +232,86 @@ def test_python_level_size_check():
         _lib._check_levels(tiled, BN, H, W, "out", tiled=False, exact=True)
     with pytest.raises(ValueError, match="levels"):
         _lib._check_levels(rowmajor * 3, BN, H, W, "pyr", tiled=False)
+
+
+# corr_voxel_grid(x, y, t, p, M, C, H, W, normalize, out, ws, ws_bytes, stream),
+# corr_voxel_grid_tbilinear(events, M, C, H, W, normalize, out, ws, ws_bytes, stream) and
+# corr_forward_splat(flow, B, H, W, out, ws, ws_bytes, stream): every refusal below is
+# CORR_EINVAL with a message; any HIP call would fail differently on a machine without a GPU.
+_P = 256          # a well-aligned non-null pointer that is never dereferenced
+_BIG = 1 << 40
+
+
+def _refused(lib, rc, msg):
+    err = lib.corr_last_error().decode()
+    return rc == -1 and msg in err and len(err) > len(msg)
+
+
+def test_voxel_workspace_sizes(lib):
+    """The workspace functions: 0 on a negative event count or a zero dimension; otherwise at
+    least the three per-cell int32 arrays plus one int32 per entry (4 per DSEC event, 2 per
+    MVSEC event), and growing with either."""
+    for f, sides in ((lib.corr_voxel_grid_workspace, 4), (lib.corr_voxel_grid_tbilinear_workspace, 2)):
+        for bad in ((-1, 5, 6, 8), (10, 0, 6, 8), (10, 5, 0, 8), (10, 5, 6, 0), (10, -5, 6, 8)):
+            assert f(*bad) == 0, bad
+        for M, C, H, W in ((0, 5, 6, 8), (1, 5, 6, 8), (20000, 9, 1000, 933)):
+            assert f(M, C, H, W) >= 3 * C * H * W * 4 + sides * M * 4
+        assert f(2000, 5, 6, 8) > f(1000, 5, 6, 8) and f(10, 5, 60, 80) > f(10, 5, 6, 8)
+    for bad in ((0, 6, 8), (1, 0, 8), (1, 6, 0), (-1, 6, 8)):
+        assert lib.corr_forward_splat_workspace(*bad) == 0, bad
+    assert lib.corr_forward_splat_workspace(2, 17, 23) >= 7 * 2 * 17 * 23 * 4
+
+
+def test_voxel_grid_rejects_bad_arguments(lib):
+    need = lib.corr_voxel_grid_workspace(10, 5, 6, 8)
+    call = lambda x=_P, y=_P, t=_P, p=_P, M=10, C=5, H=6, W=8, out=_P, ws=_P, wsb=need: lib.corr_voxel_grid(  # noqa: E731
+        x, y, t, p, M, C, H, W, 1, out, ws, wsb, None)
+    assert _refused(lib, call(M=-1), "n_events >= 0")
+    for dim in ("C", "H", "W"):
+        assert _refused(lib, call(**{dim: 0}), "C, H, W >= 1"), dim
+    assert _refused(lib, call(M=1 << 29, wsb=_BIG), "too large")             # 4 M = 2^31 entries
+    assert not _refused(lib, call(M=(1 << 29) - 1, wsb=16), "too large")     # one fewer: the next check speaks
+    assert _refused(lib, call(M=(1 << 29) - 1, wsb=16), "workspace")
+    assert _refused(lib, call(C=2, H=1 << 15, W=1 << 15, wsb=_BIG), "too large")   # 2^31 cells
+    assert _refused(lib, call(wsb=need - 1), "workspace")
+    assert _refused(lib, call(ws=None), "workspace")
+    assert _refused(lib, call(out=None), "out is NULL")
+    for name in ("x", "y", "t", "p"):
+        assert _refused(lib, call(**{name: None}), f"{name} is NULL"), name
+    assert _refused(lib, call(x=_P + 2), "x is not 4-byte aligned")
+    # M = 0 needs no event pointers, but still an out and a workspace
+    need0 = lib.corr_voxel_grid_workspace(0, 5, 6, 8)
+    assert _refused(lib, call(x=None, y=None, t=None, p=None, M=0, wsb=need0 - 1), "workspace")
+    assert _refused(lib, call(x=None, y=None, t=None, p=None, M=0, out=None, wsb=need0), "out is NULL")
+
+
+def test_voxel_grid_tbilinear_rejects_bad_arguments(lib):
+    need = lib.corr_voxel_grid_tbilinear_workspace(10, 5, 6, 8)
+    call = lambda ev=_P, M=10, C=5, H=6, W=8, out=_P, ws=_P, wsb=need: lib.corr_voxel_grid_tbilinear(  # noqa: E731
+        ev, M, C, H, W, 1, out, ws, wsb, None)
+    assert _refused(lib, call(M=-1), "n_events >= 0")
+    for dim in ("C", "H", "W"):
+        assert _refused(lib, call(**{dim: 0}), "C, H, W >= 1"), dim
+    assert _refused(lib, call(M=1 << 30, wsb=_BIG), "too large")             # 2 M = 2^31 entries
+    assert _refused(lib, call(M=(1 << 30) - 1, wsb=16), "workspace")
+    assert _refused(lib, call(C=2, H=1 << 15, W=1 << 15, wsb=_BIG), "too large")
+    assert _refused(lib, call(wsb=need - 1), "workspace")
+    assert _refused(lib, call(ws=None), "workspace")
+    assert _refused(lib, call(out=None), "out is NULL")
+    assert _refused(lib, call(ev=None), "events is NULL")
+    assert _refused(lib, call(ev=_P + 4), "events is not 8-byte aligned")
+    need0 = lib.corr_voxel_grid_tbilinear_workspace(0, 5, 6, 8)
+    assert _refused(lib, call(ev=None, M=0, wsb=need0 - 1), "workspace")
+
+
+def test_forward_splat_rejects_bad_arguments(lib):
+    need = lib.corr_forward_splat_workspace(2, 17, 23)
+    call = lambda flow=_P, B=2, H=17, W=23, out=_P, ws=_P, wsb=need: lib.corr_forward_splat(  # noqa: E731
+        flow, B, H, W, out, ws, wsb, None)
+    for dim, v in (("B", 0), ("B", -1), ("H", 0), ("W", 0)):
+        assert _refused(lib, call(**{dim: v}), "B, H, W must be >= 1"), dim
+    assert _refused(lib, call(B=1, H=23171, W=23171, wsb=_BIG), "too large")  # 4 H W >= 2^31 entries
+    assert _refused(lib, call(wsb=need - 1), "workspace")
+    assert _refused(lib, call(ws=None), "workspace")
+    assert _refused(lib, call(out=None), "out is NULL")
+    assert _refused(lib, call(flow=None), "flow is NULL")

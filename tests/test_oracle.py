@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import prng
-from _util import REL_TOL, bit_equal, golden_names, load, norm_rel
+from _util import REL_TOL, bit_equal, golden_names, load, norm_rel, voxel_edge_cases, voxel_norm_within_bar
 from oracle import oracle, torch_ops
 
 BUILD_CASES = [n for n in golden_names() if not n.startswith(("g_bwd", "g_dsec", "g_e2e", "g_splat", "g_voxel"))]
@@ -166,3 +166,52 @@ def test_oracle_voxel_grid_matches_reference_golden():
         assert bit_equal(oracle.voxel_grid(g[f"ev_{t}"], C, H, W, False), g[f"raw_{t}"]), t
         n, ref = oracle.voxel_grid(g[f"ev_{t}"], C, H, W, True), g[f"norm_{t}"]
         assert np.abs(n - ref).max() <= 1e-6 * np.abs(ref).max(), t
+
+
+def _check_edge_case(fn, g, kind, tag):
+    M, C, H, W = (int(v) for v in g[f"{kind}_meta_{tag}"])
+    ev, raw, ref = g[f"{kind}_ev_{tag}"], g[f"{kind}_raw_{tag}"], g[f"{kind}_norm_{tag}"]
+    assert bit_equal(fn(ev, C, H, W, False), raw), tag
+    assert voxel_norm_within_bar(fn(ev, C, H, W, True), ref), tag
+    if tag in ("one_cell", "equal_cells") or not raw.any():
+        assert not fn(ev, C, H, W, True).any(), tag
+
+
+def test_voxel_edges_fixture_is_what_it_says():
+    """The fixture holds what its generator promises: zero grids for the windows with
+    t[M-1] == t[0], zero normalised grids where one cell (or equal cells) is all there is, a
+    NaN cell that spreads to every nonzero cell, and the cancelled cell left out of the mean
+    (2/3, not 1/2: the cell of value 1 maps to (1 - 2/3) / std({2, 1, -1}))."""
+    g = load("g_voxel_edges")
+    assert len(voxel_edge_cases(g, "d")) == 13 and len(voxel_edge_cases(g, "m")) == 5
+    for tag in ("single", "single_nan_t", "equal_stamps", "ends_equal", "ends_equal_neg"):
+        assert not g[f"d_raw_{tag}"].any() and not g[f"d_norm_{tag}"].any(), tag
+    for k in ("d", "m"):
+        for tag in ("one_cell", "equal_cells"):
+            assert g[f"{k}_raw_{tag}"].any() and not g[f"{k}_norm_{tag}"].any(), (k, tag)
+        raw, nrm = g[f"{k}_raw_cancelled"], g[f"{k}_norm_cancelled"]
+        assert sorted(raw[raw != 0]) == [-1.0, 1.0, 2.0]
+        sd = np.std([2.0, 1.0, -1.0], ddof=1)
+        assert abs(float(nrm[raw == 1.0][0]) - (1.0 - 2.0 / 3.0) / sd) < 1e-6
+    raw, nrm = g["d_raw_nan_cell"], g["d_norm_nan_cell"]
+    assert np.isnan(raw).any() and np.isfinite(raw[raw != 0]).any()
+    assert np.isnan(nrm[raw != 0]).all() and not nrm[raw == 0].any()
+    assert np.isfinite(g["d_raw_nan_coords"]).all()
+
+
+def test_oracle_voxel_grid_edges_match_reference_golden():
+    """oracle_voxel_grid on every VoxelGrid case of g_voxel_edges (degenerate windows, NaN / inf
+    / beyond-int32 coordinates, corners and bins outside the grid, odd polarities, the
+    normalisation's branches): raw grid bit-identical, normalised grid within 1e-6 of max|v|
+    with the reference's zero and NaN pattern."""
+    g = load("g_voxel_edges")
+    for tag in voxel_edge_cases(g, "d"):
+        _check_edge_case(oracle.voxel_grid, g, "d", tag)
+
+
+def test_oracle_voxel_grid_tbilinear_edges_match_reference_golden():
+    """oracle_voxel_grid_tbilinear on the MVSEC cases of g_voxel_edges (flat indices that wrap
+    into a neighbouring row, a NaN stamp, the normalisation's branches): same bars."""
+    g = load("g_voxel_edges")
+    for tag in voxel_edge_cases(g, "m"):
+        _check_edge_case(oracle.voxel_grid_tbilinear, g, "m", tag)
