@@ -76,7 +76,10 @@ def test_e2e_flow_matches_reference(monkeypatch):
 @pytest.mark.gpu
 def test_e2e_training_step_runs_through_hip_backward():
     """Config 4 shape (288x384 crops, B=2 here): forward + sequence-loss backward through
-    the HIP CorrBlock; gradients reach the feature encoder and are finite."""
+    the HIP CorrBlock; gradients reach the feature encoder and are finite.  Every parameter's
+    gradient is present and finite, and non-zero unless it is 0 in exact arithmetic (the bias of
+    a convolution that feeds an instance norm or a train-mode batch norm, _train_ref.py)."""
+    from _train_ref import structural_zero
     dev = "cuda:0"
     model = _model(15).to(dev).train()
     im1 = torch.from_numpy(prng.voxel_grid(1, (2, 15, 288, 384))).to(dev)
@@ -87,6 +90,11 @@ def test_e2e_training_step_runs_through_hip_backward():
     loss.backward()
     g = model.fnet.conv1.weight.grad
     assert g is not None and torch.isfinite(g).all() and g.abs().sum() > 0
+    zeros = structural_zero(model)
+    assert len(zeros) == 30
+    for name, p in model.named_parameters():
+        assert p.grad is not None and torch.isfinite(p.grad).all(), name
+        assert name in zeros or p.grad.abs().sum() > 0, name
 
 
 @pytest.mark.gpu
