@@ -140,7 +140,8 @@ size_t corr_build_workspace(int algo, int B, int D, int NQ, int H, int W);
 
 /*
  * corr_build_rows with an explicit algorithm and caller-allocated workspace (>= the size
- * corr_build_workspace returns; it may be reused across calls on the same stream).
+ * corr_build_workspace returns, 256-byte aligned, also for corr_build_region; it may be reused
+ * across calls on the same stream).
  * CORR_EUNSUPPORTED if `algo` cannot handle D.
  */
 int corr_build_ex(int algo, const float *fmap1_rows, int NQ, const float *fmap2, int B, int D,
@@ -443,7 +444,9 @@ int corr_ondemand_lookup_conv(const void *workspace, const float *coords, int B,
  * exact three-piece split of CORR_BUILD_BF16X6 (six products per fp32 product, no scales);
  * dW and the bias sum per-workgroup partials in a fixed order (deterministic).  packed_weight
  * from corr_lookup_conv_weights; workspace of corr_lookup_conv_bwd_workspace(B, H, W, levels)
- * bytes (16-B aligned) when grad_weight or grad_bias is requested.  radius 4, levels <= 4.
+ * bytes (16-B aligned) when grad_weight or grad_bias is requested.  When H*W is a multiple of 4
+ * the kernels take 16-byte loads of grad_out and (with relu) out, which must then be 16-byte
+ * aligned (CORR_EINVAL otherwise).  radius 4, levels <= 4.
  */
 size_t corr_lookup_conv_bwd_workspace(int B, int H, int W, int levels);
 int corr_lookup_conv_bwd(const float *const *pyr, const float *coords, int B, int H, int W, int levels, int radius,

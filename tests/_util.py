@@ -2,12 +2,17 @@
 import os
 
 import numpy as np
+import torch
+
+import prng
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 # north_star: "fp32 correlation and lookup within 1e-4 relative", defined as the
 # norm-relative error ||a - b||_inf / ||b||_inf.
 REL_TOL = 1e-4
+
+DEV = "cuda:0"
 
 
 def load(name):
@@ -86,3 +91,20 @@ def build_level0(t1, t2, algo, ws=None):
     lv = tiled_levels(B, H, W, 1, t1.device, NQ=t1.shape[2] * t1.shape[3])
     _lib.build(t1, t2, lv, algo, ws)
     return export_levels(lv, H, W)[0].reshape(-1, H * W)
+
+
+def _bwd_case(T, B, H, W, L, r, seed):
+    """T lookups' coords (mixed regular / pixel-grid / far taps) and upstream gradients."""
+    K = (2 * r + 1) ** 2
+    cs, gs = [], []
+    for t in range(T):
+        c = prng.lookup_coords(seed + t, B, H, W, 0.7 * t)
+        if t % 3 == 1:  # integer grid: the general range-gather path
+            ys, xs = np.meshgrid(np.arange(H, dtype=np.float32), np.arange(W, dtype=np.float32), indexing="ij")
+            c[:, 0], c[:, 1] = xs, ys
+        if t % 5 == 2:  # far taps: the sequential scatter path
+            c[0, 0, 1, :2] = [1048000.5, -3.25]
+        c[0, :, 0, t % W] = np.float32(np.nan)
+        cs.append(torch.from_numpy(c).to(DEV))
+        gs.append(torch.from_numpy(prng.gauss(seed + 100 + t, (B, L * K, H, W))).to(DEV))
+    return cs, gs

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import prng
-from _util import REL_TOL, bit_equal, build_level0, export_levels, golden_names, load, norm_rel, tiled_levels
+from _util import REL_TOL, _bwd_case, bit_equal, build_level0, export_levels, golden_names, load, norm_rel, tiled_levels
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -761,23 +761,6 @@ def test_lookup_bwd_bitexact_vs_oracle(B, D, H, W, L, r, kind):
     _lib.pool_bwd(gl, H, W)
     for l in range(L):
         assert bit_equal(gl[l].cpu().numpy(), ref[l]), l
-
-
-def _bwd_case(T, B, H, W, L, r, seed):
-    """T lookups' coords (mixed regular / pixel-grid / far taps) and upstream gradients."""
-    K = (2 * r + 1) ** 2
-    cs, gs = [], []
-    for t in range(T):
-        c = prng.lookup_coords(seed + t, B, H, W, 0.7 * t)
-        if t % 3 == 1:  # integer grid: the general range-gather path
-            ys, xs = np.meshgrid(np.arange(H, dtype=np.float32), np.arange(W, dtype=np.float32), indexing="ij")
-            c[:, 0], c[:, 1] = xs, ys
-        if t % 5 == 2:  # far taps: the sequential scatter path
-            c[0, 0, 1, :2] = [1048000.5, -3.25]
-        c[0, :, 0, t % W] = np.float32(np.nan)
-        cs.append(torch.from_numpy(c).to(DEV))
-        gs.append(torch.from_numpy(prng.gauss(seed + 100 + t, (B, L * K, H, W))).to(DEV))
-    return cs, gs
 
 
 @pytest.mark.parametrize("T", [0, 1, 3, 12, 40])
