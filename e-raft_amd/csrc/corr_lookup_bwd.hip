@@ -33,6 +33,9 @@ struct LookupBwdSmem {
 
 constexpr int lookup_bwd_threads(int S, int BQ) { return (BQ * (S + 2) + 63) / 64 * 64; }
 constexpr int kBwdQB = 64;  // queries per workgroup (32: 4 workgroups per CU but 10% slower, measured)
+// ... halved where 64 queries' S + 2 columns exceed a workgroup's 1024 threads (radius 7: 1088).
+// The per-query sums do not depend on the workgroup's other queries, whichever form it takes.
+constexpr int lookup_bwd_qb(int S) { return lookup_bwd_threads(S, kBwdQB) <= 1024 ? kBwdQB : kBwdQB / 2; }
 
 // Backward, three phases (BQ queries; thread (q, t) = (tid % BQ, tid / BQ), t < S + 2):
 //   1. thread (q, t < S): tap t of query q on both axes + the gradient row of x-tap t -> LDS;
@@ -292,9 +295,11 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float *__restrict__
 template <int S>
 hipError_t launch_lookup_bwd_s(const BwdLookups &lk, int B, int NQ, int H, int W, int L, const LevelPtrs &gpyr,
                                hipStream_t s) {
-    const int nqb = (NQ + kBwdQB - 1) / kBwdQB;
-    hipLaunchKernelGGL((lookup_bwd_kernel<S, kBwdQB>), dim3(nqb * B, L), dim3(lookup_bwd_threads(S, kBwdQB)), 0, s,
-                       lk, B, NQ, H, W, L, gpyr);
+    constexpr int QB = lookup_bwd_qb(S);
+    static_assert(lookup_bwd_threads(S, QB) <= 1024, "a workgroup has at most 1024 threads");
+    const int nqb = (NQ + QB - 1) / QB;
+    hipLaunchKernelGGL((lookup_bwd_kernel<S, QB>), dim3(nqb * B, L), dim3(lookup_bwd_threads(S, QB)), 0, s, lk, B, NQ,
+                       H, W, L, gpyr);
     return hipGetLastError();
 }
 

@@ -45,6 +45,8 @@ def _load():
         lib.oracle_lookup_rows.argtypes = [vp, vp, i, i, i, i, i, i, vp]
         lib.oracle_lookup_rows.restype = None
         lib.oracle_lookup_bwd.argtypes = [vp, vp, i, i, i, i, i, vp]
+        lib.oracle_lookup_bwd_rows.argtypes = [vp, vp, i, i, i, i, i, i, vp]
+        lib.oracle_lookup_bwd_rows.restype = None
         lib.oracle_pool_bwd.argtypes = [vp, l, i, i, i]
         lib.oracle_corr_bwd.argtypes = [vp, vp, vp, i, i, i, vp, vp]
         lib.oracle_forward_splat.argtypes = [vp, i, i, i, vp]
@@ -140,6 +142,23 @@ def lookup_bwd(coords, grad_out, grad_pyr, radius=4):
         assert g.dtype == np.float32 and g.flags.c_contiguous
     _load().oracle_lookup_bwd(_p(coords), _p(grad_out), B, H, W, len(grad_pyr), radius,
                               _ptr_array(grad_pyr))
+    return grad_pyr
+
+
+def lookup_bwd_rows(coords_rows, grad_rows, grad_pyr, H, W, radius=4):
+    """lookup_bwd for a query-row slab: coords [B, 2, rows, Wq] and gradients [B, L*K, rows, Wq],
+    accumulated into grad_pyr (list, modified in place), the gradient pyramid of the (H, W) target
+    map whose levels are [B*rows*Wq, 1, H>>l, W>>l]."""
+    coords_rows, grad_rows = _c(coords_rows), _c(grad_rows)
+    B = coords_rows.shape[0]
+    NQ = int(np.prod(coords_rows.shape[2:]))
+    L = len(grad_pyr)
+    assert grad_rows.shape == (B, L * (2 * radius + 1) ** 2) + coords_rows.shape[2:], grad_rows.shape
+    for l, g in enumerate(grad_pyr):
+        assert g.dtype == np.float32 and g.flags.c_contiguous
+        assert g.size == B * NQ * (H >> l) * (W >> l), (l, g.shape)
+    _load().oracle_lookup_bwd_rows(_p(coords_rows), _p(grad_rows), B, NQ, H, W, L, radius,
+                                   _ptr_array(grad_pyr))
     return grad_pyr
 
 

@@ -108,3 +108,54 @@ def _bwd_case(T, B, H, W, L, r, seed):
         cs.append(torch.from_numpy(c).to(DEV))
         gs.append(torch.from_numpy(prng.gauss(seed + 100 + t, (B, L * K, H, W))).to(DEV))
     return cs, gs
+
+
+def cell_magnitude(coords_list, abs_grads_list, H, W, L, r):
+    """M [B*NQ, 1, H, W]: the fp32 oracle's lookup_bwd over all lookups applied to |g|, then
+    pool_bwd.  Bilinear weights are non-negative, so M is a sum of non-negative terms that bounds
+    sum |contribution| of every level-0 cell of dC; a cell no window touches has M = 0.  The
+    coords may be a query-row slab [B, 2, rows, Wq] of the (H, W) map."""
+    from oracle import oracle
+    B = coords_list[0].shape[0]
+    NQ = int(np.prod(coords_list[0].shape[2:]))
+    gp = [np.zeros((B * NQ, 1, h, w), np.float32) for h, w in oracle.level_shapes(H, W, L)]
+    for c, g in zip(coords_list, abs_grads_list):
+        oracle.lookup_bwd_rows(np.asarray(c, np.float32), np.abs(np.asarray(g, np.float32)), gp, H, W, r)
+    oracle.pool_bwd(gp, H, W)
+    return gp[0]
+
+
+def cell_bound_k(T, L):
+    """k of within_cell_bound.  Consecutive taps are 1 +- 1 ulp apart, so at most 3 taps per axis
+    have their floor in {x - 1, x}: a cell collects at most 9 corner contributions per lookup and
+    level.  T * L of those, L - 1 fold additions and 3 roundings inside a product give each path's
+    first-order error <= (9 T L + L + 3) * 2^-24 * M; two such paths are compared, hence the 2."""
+    return 2 * (9 * T * L + L + 3)
+
+
+def cell_ratio(a, b, M):
+    """max |a - b| / (2^-24 * M) over the finite cells with M > 0 (0.0 when there is none)."""
+    a, b, M = (np.asarray(t, np.float64).reshape(-1) for t in (a, b, M))
+    sel = np.isfinite(a) & np.isfinite(b) & (M > 0)
+    return float((np.abs(a[sel] - b[sel]) / (2.0 ** -24 * M[sel])).max(initial=0.0))
+
+
+def within_cell_bound(a, b, M, T, L):
+    """|a - b| <= k * (2^-24 * M + 2^-149) in every cell, k = cell_bound_k(T, L) (the 2^-149 term:
+    k denormal steps where products underflow); where M = 0 no window touches the cell, and a and b
+    must be bit-identical there; a and b must have the same non-finite cells, which are not
+    compared further.  M: cell_magnitude of the same lookups."""
+    a32 = np.ascontiguousarray(a, np.float32).reshape(-1)
+    b32 = np.ascontiguousarray(b, np.float32).reshape(-1)
+    M = np.asarray(M, np.float64).reshape(-1)
+    if not (a32.shape == b32.shape == M.shape):
+        return False
+    if not (np.array_equal(np.isnan(a32), np.isnan(b32)) and np.array_equal(np.isposinf(a32), np.isposinf(b32))
+            and np.array_equal(np.isneginf(a32), np.isneginf(b32))):
+        return False
+    untouched = (M == 0) & ~np.isnan(b32)
+    if not np.array_equal(a32.view(np.uint32)[untouched], b32.view(np.uint32)[untouched]):
+        return False
+    fin = np.isfinite(b32) & ~untouched
+    d = np.abs(a32[fin].astype(np.float64) - b32[fin].astype(np.float64))
+    return bool((d <= cell_bound_k(T, L) * (2.0 ** -24 * M[fin] + 2.0 ** -149)).all())

@@ -4,12 +4,15 @@ vectors and the oracle, on an MI355X.  Run on the GPU box: pytest -m gpu.
 Bars (north_star): correlation within 1e-4 norm-relative; pooling and lookup BIT-EXACT on
 identical inputs; backward within 1e-4 norm-relative.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import prng
-from _util import REL_TOL, _bwd_case, bit_equal, build_level0, export_levels, golden_names, load, norm_rel, tiled_levels
+from _util import (REL_TOL, _bwd_case, bit_equal, build_level0, cell_bound_k, cell_magnitude, cell_ratio, export_levels,
+                   golden_names, load, norm_rel, tiled_levels, within_cell_bound)
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +41,14 @@ def _fmaps(meta, dev=DEV):
 
 
 ALGOS = ["bf16x6", "f16x3", "fp32"]
+
+
+@functools.lru_cache(maxsize=8)
+def _bwd_case_magnitude(T, B, H, W, L, r, seed):
+    """cell_magnitude (the per-cell scale of within_cell_bound) of _bwd_case's lookups, computed on
+    the CPU oracle once per case."""
+    cs, gs = _bwd_case(T, B, H, W, L, r, seed)
+    return cell_magnitude([c.cpu().numpy() for c in cs], [g.cpu().numpy() for g in gs], H, W, L, r)
 
 
 @pytest.mark.parametrize("algo", ALGOS)
@@ -801,13 +812,17 @@ def test_lookup_bwd_multi_and_fold_bitexact(T, B, H, W, L, r):
                                            (1, 16, 64, 96, 5, 2, 2), (1, 8, 120, 160, 4, 4, 2)])
 def test_corr_backward_matches_staged_path(algo, B, D, H, W, L, r, T, exact):
     """corr_backward against the staged path (lookup_bwd per lookup, pool_bwd, build_bwd with its
-    own absmax).  Covers the fused LDS-resident kernel at workgroup sizes 8 (18x24, 36x48), 4
-    (60x80), 1 (120x160) queries, and the multi-lookup + fold fallback (33 lookups > one launch's
-    table; 5 levels), and a ragged last query group (17x23 at r = 4: the quad-transposed gradient
-    loads of a partial group).  exact (CORR_BACKWARD_EXACT_FOLD): bit-identical.  Default: the fused fold's
-    separable closed form at r = 4 (the same per-tap weights, another rounding order): dC within
-    1e-6 norm-relative of the staged path (the verdict's bar; seen ~1e-7) and dfmap1 / dfmap2
-    within 1e-6; the other radii and the fallback stay bit-identical."""
+    own absmax).  Covers the fused LDS-resident kernel, whose query count per workgroup depends on
+    the radius alone (FusedStage<S>::BQ: 4 at r = 4, 8 at r = 2 and 3), up to 60x80, and the
+    multi-lookup + fold fallback (33 lookups > one launch's table; 5 levels; 120x160, whose
+    workgroup image exceeds the 160 KiB of LDS), and a ragged last query group (17x23 at r = 4: the
+    quad-transposed gradient loads of a partial group).  exact (CORR_BACKWARD_EXACT_FOLD):
+    bit-identical.  Default: the fused fold's separable closed form at r = 4 (the same per-tap
+    weights, another rounding order): dC within 1e-6 norm-relative of the staged path (the
+    verdict's bar; seen ~1e-7) and within the per-cell bound of _util.within_cell_bound (norm_rel
+    alone cannot see a wrong cell below 1e-6 of the largest; at 120x160, whose dC is 1.5 GB, the
+    fallback's dC is bit-identical instead), and dfmap1 / dfmap2 within 1e-6; the other radii and the
+    fallback stay bit-identical."""
     from eraft_amd import _lib
     from eraft_amd.corr import _alloc_grad_pyramid
     f1 = torch.from_numpy(prng.gauss(61, (B, D, H, W))).to(DEV)
@@ -829,6 +844,13 @@ def test_corr_backward_matches_staged_path(algo, B, D, H, W, L, r, T, exact):
             e = norm_rel(a.cpu().numpy(), b.cpu().numpy())
             print(f"{'dC dF1 dF2'.split()[k]}: {e:.2e}")
             assert e <= 1e-6, (k, e)
+        if H * W <= 60 * 80:
+            M = _bwd_case_magnitude(T, B, H, W, L, r, 800)
+            a, b = got[0].cpu().numpy(), ref[0].cpu().numpy()
+            print(f"dC: max |a - b| / (2^-24 M) = {cell_ratio(a, b, M):.3f} (k = {cell_bound_k(T, L)})")
+            assert within_cell_bound(a, b, M, T, L)
+        else:  # the staged fallback: identical words pass the bound whatever M is (compared on the GPU)
+            assert torch.equal(got[0].view(torch.int32), ref[0].view(torch.int32))
 
 
 @pytest.mark.parametrize("exact", [True, False])
@@ -894,11 +916,25 @@ def test_autograd_separable_fold_close_to_per_lookup(monkeypatch):
     """CorrBlock autograd with the default fused fold (separable closed form) against the
     per-lookup path (ERAFT_AMD_FUSED_BWD=0, the reference's scatter order): fmap gradients within
     1e-6 norm-relative at the train shape's width (36x48, 12 lookups, the first on the integer
-    grid as at a cold start)."""
+    grid as at a cold start); and the dC that each path hands to its GEMMs (corr_backward's level
+    0, build_bwd's argument) within the per-cell bound of _util.within_cell_bound."""
+    from eraft_amd import _lib
     B, D, H, W, L, r, T = 2, 64, 36, 48, 4, 4, 12
     f1n, f2n = prng.gauss(73, (B, D, H, W)), prng.gauss(74, (B, D, H, W))
     cs, gs = _bwd_case(T, B, H, W, L, r, 910)
-    res = {}
+    res, dc = {}, {}
+    fused, staged = _lib.backward, _lib.build_bwd
+
+    def spy_backward(coords_list, grad_list, radius, grad_levels, *a, **k):
+        out = fused(coords_list, grad_list, radius, grad_levels, *a, **k)
+        dc["1"] = grad_levels[0].cpu().numpy()
+        return out
+
+    def spy_build_bwd(grad_c, *a, **k):
+        dc["0"] = grad_c.cpu().numpy()
+        return staged(grad_c, *a, **k)
+    monkeypatch.setattr(_lib, "backward", spy_backward)
+    monkeypatch.setattr(_lib, "build_bwd", spy_build_bwd)
     monkeypatch.setenv("ERAFT_AMD_EXACT_FOLD", "0")
     for mode in ("1", "0"):
         monkeypatch.setenv("ERAFT_AMD_FUSED_BWD", mode)
@@ -911,6 +947,10 @@ def test_autograd_separable_fold_close_to_per_lookup(monkeypatch):
         e = norm_rel(a, b)
         print(f"dF{k + 1}: {e:.2e}")
         assert e <= 1e-6, (k, e)
+    assert sorted(dc) == ["0", "1"] and dc["1"].shape == dc["0"].shape
+    M = _bwd_case_magnitude(T, B, H, W, L, r, 910)
+    print(f"dC: max |a - b| / (2^-24 M) = {cell_ratio(dc['1'], dc['0'], M):.3f} (k = {cell_bound_k(T, L)})")
+    assert within_cell_bound(dc["1"], dc["0"], M, T, L)
 
 
 def test_autograd_fused_backward_equals_per_lookup(monkeypatch):
