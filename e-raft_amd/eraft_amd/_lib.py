@@ -190,7 +190,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
               "corr_build_rows", "corr_lookup_rows", "corr_lookup_bwd_rows", "corr_build_bwd_rows",
               "corr_build_ex", "corr_build_bwd_ex", "corr_forward_splat",
               "corr_convex_upsample", "corr_voxel_grid", "corr_lookup_conv", "corr_lookup_conv_weights",
-              "corr_voxel_grid_tbilinear", "corr_lookup_bwd_multi", "corr_pool_fold", "corr_backward_workspace",
+              "corr_voxel_grid_tbilinear", "corr_lookup_bwd_multi", "corr_pool_fold",
               "corr_backward", "corr_convex_upsample_bwd", "corr_lookup_conv_bwd", "corr_pyramid_export",
               "corr_pyramid_import"):
         getattr(lib, f).restype = i
