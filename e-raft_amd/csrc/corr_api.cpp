@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "../../include/corr_mi355x_train.h"
 #include "corr_common.h"
 
 namespace corr {
@@ -1168,6 +1169,126 @@ int corr_build_bwd(const float *grad_c, const float *fmap1, const float *fmap2, 
                    size_t workspace_bytes, void *stream) {
     return corr_build_bwd_rows(grad_c, fmap1, H * W, fmap2, B, D, H, W, dfmap1, dfmap2, workspace,
                                workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+// ---- include/corr_mi355x_train.h: the sequence loss, alone and fused with the convex upsampling ----
+namespace corr {
+
+static int check_ptr8(const char *fn, const void *p, const char *name) {
+    if (!p) return fail(CORR_EINVAL, "%s: %s is NULL", fn, name);
+    if ((uintptr_t)p % 8) return fail(CORR_EINVAL, "%s: %s is not 8-byte aligned", fn, name);
+    return CORR_OK;
+}
+
+static int check_max_flow(const char *fn, float max_flow) {
+    if (!(max_flow > 0.0f) || max_flow > 3.402823466e38f)
+        return fail(CORR_EINVAL, "%s: max_flow must be finite and positive (got %g)", fn, (double)max_flow);
+    return CORR_OK;
+}
+
+// The loss frame H x W of N items: sizes, and every tensor of it int-indexable.
+static int check_loss_frame(const char *fn, int N, int H, int W) {
+    if (N < 1) return fail(CORR_EINVAL, "%s: N must be >= 1 (got %d)", fn, N);
+    if (H < 1 || W < 1) return fail(CORR_EINVAL, "%s: H, W must be >= 1 (got %d, %d)", fn, H, W);
+    if ((long double)N * 2 * H * W >= (long double)(1LL << 31))
+        return fail(CORR_EINVAL, "%s: N*2*H*W too large (2^31 elements or more)", fn);
+    return CORR_OK;
+}
+
+static int check_upsample_loss(const char *fn, int N, int h, int w, int H, int W, float max_flow) {
+    if (N < 1 || h < 1 || w < 1)
+        return fail(CORR_EINVAL, "%s: N, h, w must be >= 1 (got %d, %d, %d)", fn, N, h, w);
+    if ((long double)N * 576 * h * w >= (long double)(1LL << 31))
+        return fail(CORR_EINVAL, "%s: N*576*h*w too large (2^31 elements or more)", fn);
+    if (H < 1 || W < 1) return fail(CORR_EINVAL, "%s: H, W must be >= 1 (got %d, %d)", fn, H, W);
+    if (H > 8 * h || W > 8 * w)
+        return fail(CORR_EINVAL, "%s: H, W must be <= 8h, 8w = %d, %d (got %d, %d)", fn, 8 * h, 8 * w, H, W);
+    return check_max_flow(fn, max_flow);
+}
+
+static int check_workspace8(const char *fn, const void *workspace, size_t workspace_bytes, size_t need) {
+    const int rc = check_ptr8(fn, workspace, "workspace");
+    if (rc) return rc;
+    if (workspace_bytes < need)
+        return fail(CORR_EINVAL, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    return CORR_OK;
+}
+
+}  // namespace corr
+
+extern "C" {
+
+size_t corr_upsample_loss_workspace(int N, int h, int w) {
+    if (N < 1 || h < 1 || w < 1) return 0;
+    return upsample_loss_workspace(N, h, w);
+}
+
+int corr_upsample_loss(const float *flow, const float *mask, const float *gt, const float *valid, int N, int h,
+                       int w, int H, int W, float max_flow, int want_metrics, double *out, void *workspace,
+                       size_t workspace_bytes, void *stream) {
+    static const char *fn = "corr_upsample_loss";
+    g_err[0] = 0;
+    int rc = check_upsample_loss(fn, N, h, w, H, W, max_flow);
+    if (rc) return rc;
+    if ((rc = check_ptr(fn, flow, "flow")) || (rc = check_ptr(fn, mask, "mask")) || (rc = check_ptr(fn, gt, "gt")) ||
+        (rc = check_ptr(fn, valid, "valid")) || (rc = check_ptr8(fn, out, "out")) ||
+        (rc = check_workspace8(fn, workspace, workspace_bytes, upsample_loss_workspace(N, h, w))))
+        return rc;
+    return hip_status(launch_upsample_loss(flow, mask, gt, valid, N, h, w, H, W, max_flow, want_metrics != 0, out,
+                                           workspace, (hipStream_t)stream),
+                      fn);
+}
+
+int corr_upsample_loss_bwd(const float *flow, const float *mask, const float *gt, const float *valid,
+                           const float *scale, int N, int h, int w, int H, int W, float max_flow, float *dflow,
+                           float *dmask, void *workspace, size_t workspace_bytes, void *stream) {
+    static const char *fn = "corr_upsample_loss_bwd";
+    g_err[0] = 0;
+    int rc = check_upsample_loss(fn, N, h, w, H, W, max_flow);
+    if (rc) return rc;
+    if ((rc = check_ptr(fn, flow, "flow")) || (rc = check_ptr(fn, mask, "mask")) || (rc = check_ptr(fn, gt, "gt")) ||
+        (rc = check_ptr(fn, valid, "valid")) || (rc = check_ptr(fn, scale, "scale")) ||
+        (rc = check_ptr(fn, dflow, "dflow")) || (rc = check_ptr(fn, dmask, "dmask")) ||
+        (rc = check_workspace8(fn, workspace, workspace_bytes, upsample_loss_workspace(N, h, w))))
+        return rc;
+    return hip_status(launch_upsample_loss_bwd(flow, mask, gt, valid, scale, N, h, w, H, W, max_flow, dflow, dmask,
+                                               workspace, (hipStream_t)stream),
+                      fn);
+}
+
+size_t corr_sequence_loss_workspace(int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1) return 0;
+    return sequence_loss_workspace(N, H, W);
+}
+
+int corr_sequence_loss(const float *pred, const float *gt, const float *valid, int N, int H, int W, float max_flow,
+                       int want_metrics, double *out, void *workspace, size_t workspace_bytes, void *stream) {
+    static const char *fn = "corr_sequence_loss";
+    g_err[0] = 0;
+    int rc = check_loss_frame(fn, N, H, W);
+    if (rc || (rc = check_max_flow(fn, max_flow))) return rc;
+    if ((rc = check_ptr(fn, pred, "pred")) || (rc = check_ptr(fn, gt, "gt")) || (rc = check_ptr(fn, valid, "valid")) ||
+        (rc = check_ptr8(fn, out, "out")) ||
+        (rc = check_workspace8(fn, workspace, workspace_bytes, sequence_loss_workspace(N, H, W))))
+        return rc;
+    return hip_status(launch_sequence_loss(pred, gt, valid, N, H, W, max_flow, want_metrics != 0, out, workspace,
+                                           (hipStream_t)stream),
+                      fn);
+}
+
+int corr_sequence_loss_bwd(const float *pred, const float *gt, const float *valid, const float *scale, int N, int H,
+                           int W, float max_flow, float *dpred, void *stream) {
+    static const char *fn = "corr_sequence_loss_bwd";
+    g_err[0] = 0;
+    int rc = check_loss_frame(fn, N, H, W);
+    if (rc || (rc = check_max_flow(fn, max_flow))) return rc;
+    if ((rc = check_ptr(fn, pred, "pred")) || (rc = check_ptr(fn, gt, "gt")) || (rc = check_ptr(fn, valid, "valid")) ||
+        (rc = check_ptr(fn, scale, "scale")) || (rc = check_ptr(fn, dpred, "dpred")))
+        return rc;
+    return hip_status(launch_sequence_loss_bwd(pred, gt, valid, scale, N, H, W, max_flow, dpred, (hipStream_t)stream),
+                      fn);
 }
 
 }  // extern "C"

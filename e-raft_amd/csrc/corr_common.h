@@ -166,6 +166,20 @@ hipError_t launch_convex_upsample(const float *flow, const float *mask, int N, i
 size_t convex_upsample_bwd_workspace(int N, int h, int w);
 hipError_t launch_convex_upsample_bwd(const float *flow, const float *mask, const float *dout, int N, int h, int w,
                                       float *dflow, float *dmask, void *ws, hipStream_t s);
+hipError_t launch_convex_upsample_bwd_flow(const float *S, int N, int h, int w, float *dflow, hipStream_t s);
+// corr_loss.hip: the sequence loss, alone and fused with the convex upsampling
+size_t upsample_loss_workspace(int N, int h, int w);
+hipError_t launch_upsample_loss(const float *flow, const float *mask, const float *gt, const float *valid, int N,
+                                int h, int w, int H, int W, float max_flow, bool metrics, double *out, void *ws,
+                                hipStream_t s);
+hipError_t launch_upsample_loss_bwd(const float *flow, const float *mask, const float *gt, const float *valid,
+                                    const float *scale, int N, int h, int w, int H, int W, float max_flow,
+                                    float *dflow, float *dmask, void *ws, hipStream_t s);
+size_t sequence_loss_workspace(int N, int H, int W);
+hipError_t launch_sequence_loss(const float *pred, const float *gt, const float *valid, int N, int H, int W,
+                                float max_flow, bool metrics, double *out, void *ws, hipStream_t s);
+hipError_t launch_sequence_loss_bwd(const float *pred, const float *gt, const float *valid, const float *scale, int N,
+                                    int H, int W, float max_flow, float *dpred, hipStream_t s);
 size_t lookup_conv_weights_bytes();
 hipError_t launch_lookup_conv_weights(const float *w, int O, int C, void *packed, hipStream_t s);
 hipError_t launch_lookup_conv(const ConstLevelPtrs &pyr, const float *coords, int B, int NQ, int H, int W,

@@ -184,7 +184,13 @@ hipError_t launch_convex_upsample_bwd(const float *flow, const float *mask, cons
                        dmask, S);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_convex_upsample_bwd_flow(S, N, h, w, dflow, s);
+}
+
+// Pass 2 alone: also for a caller that has filled the S planes itself (corr_loss.hip).
+hipError_t launch_convex_upsample_bwd_flow(const float *S, int N, int h, int w, float *dflow, hipStream_t s) {
     const size_t total = (size_t)N * 2 * h * w;
+    if (total == 0) return hipSuccess;
     const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
     hipLaunchKernelGGL(convex_upsample_bwd_flow_kernel, dim3(grid), dim3(256), 0, s, S, N, h, w, dflow);
     return hipGetLastError();

@@ -42,6 +42,9 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
            "corr_flow_enc_weights_bytes", "corr_flow_enc_pack_weights", "corr_flow_enc_forward",
            "corr_flow_head_weights_bytes", "corr_flow_head_pack_weights", "corr_flow_head_forward",
            "corr_ondemand_lookup_conv", "corr_gru_half_step_prec", "corr_conv_forward_prec")
+# include/corr_mi355x_train.h: the sequence loss, alone and fused with the convex upsampling
+TRAIN_EXPORTS = ("corr_upsample_loss_workspace", "corr_upsample_loss", "corr_upsample_loss_bwd",
+                 "corr_sequence_loss_workspace", "corr_sequence_loss", "corr_sequence_loss_bwd")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -182,7 +185,15 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_flow_head_weights_bytes.argtypes, lib.corr_flow_head_weights_bytes.restype = [], sz
     lib.corr_flow_head_pack_weights.argtypes = [vp, vp, vp]
     lib.corr_flow_head_forward.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
-    for f in ("corr_gru_half_step_prec", "corr_conv_forward_prec"):
+    fl = ctypes.c_float
+    lib.corr_upsample_loss_workspace.argtypes, lib.corr_upsample_loss_workspace.restype = [i, i, i], sz
+    lib.corr_upsample_loss.argtypes = [vp, vp, vp, vp, i, i, i, i, i, fl, i, vp, vp, sz, vp]
+    lib.corr_upsample_loss_bwd.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, fl, vp, vp, vp, sz, vp]
+    lib.corr_sequence_loss_workspace.argtypes, lib.corr_sequence_loss_workspace.restype = [i, i, i], sz
+    lib.corr_sequence_loss.argtypes = [vp, vp, vp, i, i, i, fl, i, vp, vp, sz, vp]
+    lib.corr_sequence_loss_bwd.argtypes = [vp, vp, vp, vp, i, i, i, fl, vp, vp]
+    for f in ("corr_upsample_loss", "corr_upsample_loss_bwd", "corr_sequence_loss", "corr_sequence_loss_bwd",
+              "corr_gru_half_step_prec", "corr_conv_forward_prec"):
         getattr(lib, f).restype = i
     for f in ("corr_ondemand_lookup_conv", "corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
               "corr_flow_head_forward", "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
@@ -558,6 +569,82 @@ def convex_upsample_bwd(flow, mask, grad_out):
                                             N, h, w, _dev(dflow, "dflow"), _dev(dmask, "dmask"),
                                             ws.data_ptr(), ws.numel(), _stream(flow)))
     return dflow, dmask
+
+
+def _loss_frame(name, gt, valid, N):
+    """(H, W) of gt [N, 2, H, W] and valid [N, H, W]."""
+    if gt.dim() != 4 or gt.shape[0] != N or gt.shape[1] != 2 or tuple(valid.shape) != (N, *gt.shape[2:]):
+        raise ValueError(f"{name}: gt {tuple(gt.shape)}, valid {tuple(valid.shape)} for a batch of {N}")
+    return gt.shape[2], gt.shape[3]
+
+
+def _upsample_loss_args(name, flow, mask, gt, valid):
+    N, C, h, w = flow.shape
+    if C != 2 or tuple(mask.shape) != (N, 576, h, w):
+        raise ValueError(f"{name}: flow {tuple(flow.shape)}, mask {tuple(mask.shape)}")
+    H, W = _loss_frame(name, gt, valid, N)
+    if not (0 < H <= 8 * h and 0 < W <= 8 * w):
+        raise ValueError(f"{name}: a {H}x{W} loss frame does not lie in the {8 * h}x{8 * w} prediction")
+    return N, h, w, H, W
+
+
+def upsample_loss(flow, mask, gt, valid, max_flow, want_metrics):
+    """corr_upsample_loss: flow [N, 2, h, w], mask [N, 576, h, w], gt [N, 2, H, W], valid [N, H, W]
+    -> the six fp64 words (include/corr_mi355x_train.h) of the prediction's last H rows and W columns."""
+    N, h, w, H, W = _upsample_loss_args("upsample_loss", flow, mask, gt, valid)
+    lib = load()
+    out = torch.empty(6, dtype=torch.float64, device=flow.device)
+    ws = torch.empty((lib.corr_upsample_loss_workspace(N, h, w) + 7) // 8, dtype=torch.float64, device=flow.device)
+    with torch.cuda.device(flow.device):
+        _check(lib.corr_upsample_loss(_dev(flow, "flow"), _dev(mask, "mask"), _dev(gt, "gt"), _dev(valid, "valid"),
+                                      N, h, w, H, W, float(max_flow), int(bool(want_metrics)), out.data_ptr(),
+                                      ws.data_ptr(), ws.numel() * 8, _stream(flow)))
+    return out
+
+
+def upsample_loss_bwd(flow, mask, gt, valid, scale, max_flow):
+    """corr_upsample_loss_bwd: scale is a one-element fp32 device tensor -> (dflow, dmask)."""
+    N, h, w, H, W = _upsample_loss_args("upsample_loss_bwd", flow, mask, gt, valid)
+    if scale.numel() != 1:
+        raise ValueError(f"upsample_loss_bwd: scale must hold one float (got {tuple(scale.shape)})")
+    lib = load()
+    dflow, dmask = torch.empty_like(flow), torch.empty_like(mask)
+    ws = torch.empty((lib.corr_upsample_loss_workspace(N, h, w) + 7) // 8, dtype=torch.float64, device=flow.device)
+    with torch.cuda.device(flow.device):
+        _check(lib.corr_upsample_loss_bwd(_dev(flow, "flow"), _dev(mask, "mask"), _dev(gt, "gt"), _dev(valid, "valid"),
+                                          _dev(scale, "scale"), N, h, w, H, W, float(max_flow), _dev(dflow, "dflow"),
+                                          _dev(dmask, "dmask"), ws.data_ptr(), ws.numel() * 8, _stream(flow)))
+    return dflow, dmask
+
+
+def sequence_loss(pred, gt, valid, max_flow, want_metrics):
+    """corr_sequence_loss: pred, gt [N, 2, H, W], valid [N, H, W] -> the six fp64 words."""
+    N = pred.shape[0]
+    H, W = _loss_frame("sequence_loss", gt, valid, N)
+    if pred.shape != gt.shape:
+        raise ValueError(f"sequence_loss: pred {tuple(pred.shape)}, gt {tuple(gt.shape)}")
+    lib = load()
+    out = torch.empty(6, dtype=torch.float64, device=pred.device)
+    ws = torch.empty((lib.corr_sequence_loss_workspace(N, H, W) + 7) // 8, dtype=torch.float64, device=pred.device)
+    with torch.cuda.device(pred.device):
+        _check(lib.corr_sequence_loss(_dev(pred, "pred"), _dev(gt, "gt"), _dev(valid, "valid"), N, H, W,
+                                      float(max_flow), int(bool(want_metrics)), out.data_ptr(), ws.data_ptr(),
+                                      ws.numel() * 8, _stream(pred)))
+    return out
+
+
+def sequence_loss_bwd(pred, gt, valid, scale, max_flow):
+    """corr_sequence_loss_bwd: -> dpred = scale v sign(pred - gt)."""
+    N = pred.shape[0]
+    H, W = _loss_frame("sequence_loss_bwd", gt, valid, N)
+    if pred.shape != gt.shape or scale.numel() != 1:
+        raise ValueError(f"sequence_loss_bwd: pred {tuple(pred.shape)}, gt {tuple(gt.shape)}, scale {tuple(scale.shape)}")
+    dpred = torch.empty_like(pred)
+    with torch.cuda.device(pred.device):
+        _check(load().corr_sequence_loss_bwd(_dev(pred, "pred"), _dev(gt, "gt"), _dev(valid, "valid"),
+                                             _dev(scale, "scale"), N, H, W, float(max_flow), _dev(dpred, "dpred"),
+                                             _stream(pred)))
+    return dpred
 
 
 def voxel_grid(x, y, t, p, out, normalize):

@@ -417,7 +417,12 @@ class ERAFT(nn.Module):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in (*ts, *self.parameters())))
 
-    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True):
+    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, sequence_loss=None):
+        """`sequence_loss`: a loss.SequenceLoss.  Each iteration then hands it the 1/8-resolution
+        flow and the mask (add_upsampled: on the MI355X the loss fused with the upsampling, no
+        full-resolution prediction stored; the torch composition elsewhere) instead of calling
+        upsample_flow; the returned list of predictions is empty and the caller reads
+        sequence_loss.result().  Works under no_grad for validation."""
         image1 = self.image_padder.pad(image1).contiguous()
         image2 = self.image_padder.pad(image2).contiguous()
         fmap1, fmap2 = self.fnet([image1, image2])
@@ -443,7 +448,7 @@ class ERAFT(nn.Module):
         # made once per forward and its flow head's kernel also does the coordinate update: the loop
         # then issues no coords1 + delta and no coords1 - coords0 (flow is the kernel's flow_out)
         ub, ws, flow = self.update_block, None, None
-        for _ in range(iters):
+        for it in range(iters):
             coords1 = coords1.detach()
             if fuse:
                 enc = ub.encoder
@@ -459,6 +464,13 @@ class ERAFT(nn.Module):
                     from .update import UpdateWorkspace
                     ws = UpdateWorkspace(inp.detach())
                 kw = {"workspace": ws, "coords1": coords1, "coords0": coords0}
+            if sequence_loss is not None:
+                # the criterion needs the mask itself: the inference-only mask head fusion is not taken
+                net, up_mask, delta, *upd = ub(net, inp, corr, flow, fuse, **kw)
+                coords1, flow = upd if tail else (coords1 + delta, None)
+                sequence_loss.add_upsampled(flow if tail else coords1 - coords0, up_mask, it, iters,
+                                            (self.image_padder.pad_height, self.image_padder.pad_width))
+                continue
             if self.fuse_mask_upsample and self._mask_fusable(net, inp, corr, coords1):
                 from .upsample import channel_window, mask_upsample
                 net, hidden, delta, *upd = ub(net, inp, corr, flow, fuse, defer_mask=True, **kw)
