@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "../../include/corr_mi355x_enc_prec.h"
 #include "../../include/corr_mi355x_train.h"
 #include "corr_common.h"
 
@@ -726,12 +727,13 @@ size_t corr_enc_stats_bytes(int B, int cout, int Ho, int Wo) {
     return enc_stats_bytes(B, cout, Ho, Wo);
 }
 
-int corr_enc_conv_forward(const float *in, int cin, int B, int H, int W, int stride, const float *in_scale,
-                          const float *in_shift, int norm_per_batch, const void *packed, const float *bias,
-                          int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
-    static const char *fn = "corr_enc_conv_forward";
+static int enc_conv_forward(const char *fn, const float *in, int cin, int B, int H, int W, int stride,
+                            const float *in_scale, const float *in_shift, int norm_per_batch, const void *packed,
+                            const float *bias, int cout, float *out, void *stats, size_t stats_bytes, void *stream,
+                            int precision) {
     g_err[0] = 0;
     int rc;
+    if ((rc = check_precision(fn, precision))) return rc;
     if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if (stride != 1 && stride != 2)
         return fail(CORR_EUNSUPPORTED, "%s: built for stride 1 and 2 (got %d)", fn, stride);
@@ -755,8 +757,23 @@ int corr_enc_conv_forward(const float *in, int cin, int B, int H, int W, int str
     const long double ob = (long double)B * Ho * Wo * sizeof(float) * cout;
     if (ranges_overlap(out, ob, in, ib)) return fail(CORR_EINVAL, "%s: out must not overlap in", fn);
     return hip_status(launch_enc_conv(in, cin, B, H, W, stride, in_scale, in_shift, norm_per_batch != 0, packed, bias,
-                                      cout, out, static_cast<float *>(stats), (hipStream_t)stream),
+                                      cout, out, static_cast<float *>(stats), (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_enc_conv_forward(const float *in, int cin, int B, int H, int W, int stride, const float *in_scale,
+                          const float *in_shift, int norm_per_batch, const void *packed, const float *bias,
+                          int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
+    return enc_conv_forward("corr_enc_conv_forward", in, cin, B, H, W, stride, in_scale, in_shift, norm_per_batch,
+                            packed, bias, cout, out, stats, stats_bytes, stream, CORR_PREC_BF16X6);
+}
+
+// include/corr_mi355x_enc_prec.h
+int corr_enc_conv_forward_prec(const float *in, int cin, int B, int H, int W, int stride, const float *in_scale,
+                               const float *in_shift, int norm_per_batch, const void *packed, const float *bias,
+                               int cout, float *out, void *stats, size_t stats_bytes, int precision, void *stream) {
+    return enc_conv_forward("corr_enc_conv_forward_prec", in, cin, B, H, W, stride, in_scale, in_shift,
+                            norm_per_batch, packed, bias, cout, out, stats, stats_bytes, stream, precision);
 }
 
 // B, C, H, W of the finalize and the join: every plane and the [B][C] tables are int-indexed
@@ -841,17 +858,30 @@ static int check_enc_front(const char *fn, const float *in, int cin, int B, int 
     return CORR_OK;
 }
 
-int corr_enc_stem_forward(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
-                          int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
-    static const char *fn = "corr_enc_stem_forward";
+static int enc_stem_forward(const char *fn, const float *in, int cin, int B, int H, int W, const void *packed,
+                            const float *bias, int cout, float *out, void *stats, size_t stats_bytes, void *stream,
+                            int precision) {
     g_err[0] = 0;
     int rc;
+    if ((rc = check_precision(fn, precision))) return rc;
     if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if ((rc = check_stem_channels(fn, cout, cin))) return rc;
     if ((rc = check_enc_front(fn, in, cin, B, H, W, 2, packed, bias, cout, out, stats, stats_bytes))) return rc;
     return hip_status(launch_enc_stem(in, cin, B, H, W, packed, bias, cout, out, static_cast<float *>(stats),
-                                      (hipStream_t)stream),
+                                      (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_enc_stem_forward(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
+                          int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
+    return enc_stem_forward("corr_enc_stem_forward", in, cin, B, H, W, packed, bias, cout, out, stats, stats_bytes,
+                            stream, CORR_PREC_BF16X6);
+}
+
+int corr_enc_stem_forward_prec(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
+                               int cout, float *out, void *stats, size_t stats_bytes, int precision, void *stream) {
+    return enc_stem_forward("corr_enc_stem_forward_prec", in, cin, B, H, W, packed, bias, cout, out, stats,
+                            stats_bytes, stream, precision);
 }
 
 static int check_pw_channels(const char *fn, int cout, int cin) {
@@ -876,19 +906,33 @@ int corr_enc_pw_pack_weights(const float *w, int cout, int cin, void *packed, vo
     return hip_status(launch_enc_pw_pack(w, cout, cin, packed, (hipStream_t)stream), fn);
 }
 
-int corr_enc_pw_forward(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
-                        const float *bias, int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
-    static const char *fn = "corr_enc_pw_forward";
+static int enc_pw_forward(const char *fn, const float *in, int cin, int B, int H, int W, int stride,
+                          const void *packed, const float *bias, int cout, float *out, void *stats,
+                          size_t stats_bytes, void *stream, int precision) {
     g_err[0] = 0;
     int rc;
+    if ((rc = check_precision(fn, precision))) return rc;
     if ((rc = check_dims(fn, B, 1, H, W, 1)) || (rc = check_pixels(fn, B, H, W))) return rc;
     if (stride != 1 && stride != 2)
         return fail(CORR_EUNSUPPORTED, "%s: built for stride 1 and 2 (got %d)", fn, stride);
     if ((rc = check_pw_channels(fn, cout, cin))) return rc;
     if ((rc = check_enc_front(fn, in, cin, B, H, W, stride, packed, bias, cout, out, stats, stats_bytes))) return rc;
     return hip_status(launch_enc_pw(in, cin, B, H, W, stride, packed, bias, cout, out, static_cast<float *>(stats),
-                                    (hipStream_t)stream),
+                                    (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_enc_pw_forward(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
+                        const float *bias, int cout, float *out, void *stats, size_t stats_bytes, void *stream) {
+    return enc_pw_forward("corr_enc_pw_forward", in, cin, B, H, W, stride, packed, bias, cout, out, stats,
+                          stats_bytes, stream, CORR_PREC_BF16X6);
+}
+
+int corr_enc_pw_forward_prec(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
+                             const float *bias, int cout, float *out, void *stats, size_t stats_bytes, int precision,
+                             void *stream) {
+    return enc_pw_forward("corr_enc_pw_forward_prec", in, cin, B, H, W, stride, packed, bias, cout, out, stats,
+                          stats_bytes, stream, precision);
 }
 
 int corr_enc_join_affine(const float *y, const float *scale, const float *shift, int norm_per_batch,

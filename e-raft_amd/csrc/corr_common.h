@@ -242,7 +242,7 @@ hipError_t launch_conv_forward(const float *in_a, int ca, const float *in_b, int
 size_t enc_stats_bytes(int B, int cout, int Ho, int Wo);
 hipError_t launch_enc_conv(const float *in, int cin, int B, int H, int W, int stride, const float *scale,
                            const float *shift, int norm_per_batch, const void *packed, const float *bias, int cout,
-                           float *out, float *stats, hipStream_t s);
+                           float *out, float *stats, hipStream_t s, int precision);
 hipError_t launch_enc_finalize(const float *stats, int B, int C, int Ho, int Wo, float eps, float *scale,
                                float *shift, hipStream_t s);
 hipError_t launch_enc_join(const float *y, const float *scale, const float *shift, int norm_per_batch,
@@ -254,12 +254,12 @@ bool enc_stem_supported(int cout, int cin);
 size_t enc_stem_weights_bytes(int cout);
 hipError_t launch_enc_stem_pack(const float *w, int cout, int cin, void *packed, hipStream_t s);
 hipError_t launch_enc_stem(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
-                           int cout, float *out, float *stats, hipStream_t s);
+                           int cout, float *out, float *stats, hipStream_t s, int precision);
 bool enc_pw_supported(int cout, int cin);
 size_t enc_pw_weights_bytes(int cout, int cin);
 hipError_t launch_enc_pw_pack(const float *w, int cout, int cin, void *packed, hipStream_t s);
 hipError_t launch_enc_pw(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
-                         const float *bias, int cout, float *out, float *stats, hipStream_t s);
+                         const float *bias, int cout, float *out, float *stats, hipStream_t s, int precision);
 hipError_t launch_enc_join_affine(const float *y, const float *scale, const float *shift, int norm_per_batch,
                                   const float *skip, const float *skip_scale, const float *skip_shift,
                                   int skip_per_batch, int skip_relu, int B, int C, int H, int W, float *out,

@@ -42,10 +42,11 @@
 // Non-finite inputs give fp32's pattern (an infinite operand splits as (inf, 0, 0) and split_sum
 // keeps the infinite leading sum; tests/test_bf16x6_family.py); finite inputs give finite outputs.
 //
-// `precision` (CORR_PREC_*) selects NP for the update block's form <1, false, false>: the reduced
-// modes stage, fetch and multiply only the first two pieces (bf16x3, three products) or the first
-// one (bf16, one product, one accumulator) of both operands, from the same pack (corr_bf16x6.h,
-// DESIGN §23).  The encoder forms keep all three.
+// `precision` (CORR_PREC_*) selects NP, for the update block's form <1, false, false> and for the
+// encoder forms alike: the reduced modes stage, fetch and multiply only the first two pieces
+// (bf16x3, three products) or the first one (bf16, one product, one accumulator) of both operands,
+// from the same pack (corr_bf16x6.h).  The on-load norm is applied before the
+// split and the statistics are those of the launch's own output, in every mode.
 #include <type_traits>
 
 #include "corr_bf16x6.h"
@@ -77,8 +78,9 @@ constexpr int kConvOB = 32 * kConvT;           // output rows per workgroup
 constexpr int kConvXS = 16 + 4;                // words per LDS position: 16 channel pairs + pad (16-B rows)
 constexpr int kConvTaps = 9;
 // Waves per SIMD the kernel is compiled for, by the pieces it keeps (2: <= 256 registers; 3: <= 168).
-// One piece needs 144 registers; two pieces need 186 and spill at 168.
-constexpr int conv_waves(int np) { return np == 1 ? 3 : 2; }
+// One piece needs 144 registers; two pieces need 186 and spill at 168.  The encoder
+// forms take the third wave where the resource report shows that they fit.
+constexpr int conv_waves(int np, int stride = 1) { return np == 1 && stride == 1 ? 3 : 2; }
 constexpr int kConvRing = 6;                   // weight ring slots; divides the 18 K steps of a chunk pair
 constexpr int kConvAhead = 5;                  // K steps the weight fragments run ahead (< kConvRing)
 constexpr int kConvMaxCin = 1024;              // conv_supported's bound (the norm-on-load table in LDS)
@@ -127,12 +129,10 @@ struct ConvArgs {
 // outside the map is applied after it: the padding is zero in the normalised domain.  STATS: no
 // ReLU, and the workgroup leaves (sum, M2 about the tile's own mean) of its valid pixels per
 // output channel (header: corr_enc_conv_forward).
-// NP: the pieces kept per operand (3 = bf16x6; 2 = bf16x3 and 1 = bf16 for the update block's
-// <1, false, false> form only: products<NP>, corr_bf16x6.h).  The pack is the same for every NP:
-// a reduced mode skips the 1-KB runs of the pieces it drops.
+// NP: the pieces kept per operand (3 = bf16x6, 2 = bf16x3, 1 = bf16: products<NP>, corr_bf16x6.h).
+// The pack is the same for every NP: a reduced mode skips the 1-KB runs of the pieces it drops.
 template <int STRIDE, bool NORM_IN, bool STATS, int NP = 3>
-__global__ __launch_bounds__(kConvNT, conv_waves(NP)) void conv_kernel(ConvArgs g) {
-    static_assert(NP == 3 || (STRIDE == 1 && !NORM_IN && !STATS), "the encoder forms keep all three pieces");
+__global__ __launch_bounds__(kConvNT, conv_waves(NP, STRIDE)) void conv_kernel(ConvArgs g) {
     using G = ConvGeo<STRIDE>;
     constexpr int kConvPW = G::PW, kConvNPOS = G::NPOS, kConvStage = G::Stage, kConvNLD = G::NLD;
     __shared__ __attribute__((aligned(16))) unsigned xs[NP][kConvNPOS][kConvXS];
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(kConvNT, conv_waves(NP)) void conv_kernel(ConvArgs 
             float v[2];
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                v[c] = split_sum(acc[0][c][r], acs[0][c][r]) + bs;
+                v[c] = (NP == 1 ? acc[0][c][r] : split_sum(acc[0][c][r], acs[0][c][r])) + bs;
                 if (ok[c] && live)
                     g.out[((size_t)b * g.oc + g.off + row) * HWo + (size_t)(y0 + j0 + c) * Wo + x] = v[c];
             }
@@ -472,10 +472,26 @@ size_t enc_stats_bytes(int B, int cout, int Ho, int Wo) {
     return (size_t)B * cout * ((Ho + kConvTH - 1) / kConvTH) * ((Wo + kConvTW - 1) / kConvTW) * 2 * sizeof(float);
 }
 
+// The eight encoder forms at NP pieces: sel = 4 (stride 2) | 2 (norm on load) | 1 (statistics).
+template <int NP>
+static hipError_t launch_enc_form(int sel, const ConvArgs &g, hipStream_t s) {
+    switch (sel) {
+        case 0: return launch_conv<1, false, false, NP>(g, s);
+        case 1: return launch_conv<1, false, true, NP>(g, s);
+        case 2: return launch_conv<1, true, false, NP>(g, s);
+        case 3: return launch_conv<1, true, true, NP>(g, s);
+        case 4: return launch_conv<2, false, false, NP>(g, s);
+        case 5: return launch_conv<2, false, true, NP>(g, s);
+        case 6: return launch_conv<2, true, false, NP>(g, s);
+        default: return launch_conv<2, true, true, NP>(g, s);
+    }
+}
+
 hipError_t launch_enc_conv(const float *in, int cin, int B, int H, int W, int stride, const float *scale,
                            const float *shift, int norm_per_batch, const void *packed, const float *bias, int cout,
-                           float *out, float *stats, hipStream_t s) {
-    if (!conv_supported(cout, cin, 0) || (stride != 1 && stride != 2)) return hipErrorInvalidValue;
+                           float *out, float *stats, hipStream_t s, int precision) {
+    if (!conv_supported(cout, cin, 0) || (stride != 1 && stride != 2) || !precision_supported(precision))
+        return hipErrorInvalidValue;
     const int Ho = enc_out(H, stride), Wo = enc_out(W, stride);
     ConvArgs g{};
     g.a = g.b = in, g.bias = bias;
@@ -484,15 +500,10 @@ hipError_t launch_enc_conv(const float *in, int cin, int B, int H, int W, int st
     g.B = B, g.ca = cin, g.cb = 0, g.H = H, g.W = W, g.cout = cout, g.relu = 0, g.oc = cout, g.off = 0;
     g.tx = (Wo + kConvTW - 1) / kConvTW, g.ty = (Ho + kConvTH - 1) / kConvTH, g.nb = norm_per_batch;
     const int sel = (stride == 2 ? 4 : 0) | (scale ? 2 : 0) | (stats ? 1 : 0);
-    switch (sel) {
-        case 0: return launch_conv<1, false, false>(g, s);
-        case 1: return launch_conv<1, false, true>(g, s);
-        case 2: return launch_conv<1, true, false>(g, s);
-        case 3: return launch_conv<1, true, true>(g, s);
-        case 4: return launch_conv<2, false, false>(g, s);
-        case 5: return launch_conv<2, false, true>(g, s);
-        case 6: return launch_conv<2, true, false>(g, s);
-        default: return launch_conv<2, true, true>(g, s);
+    switch (precision) {
+        case 1: return launch_enc_form<2>(sel, g, s);
+        case 2: return launch_enc_form<1>(sel, g, s);
+        default: return launch_enc_form<3>(sel, g, s);
     }
 }
 

@@ -46,6 +46,13 @@ constexpr int kStemWords = kStemNPOS * kStemXS; // staged words per piece
 constexpr int kStemNLD = (kStemWords + kNT - 1) / kNT;  // staging passes per thread: 16, the last guarded
 constexpr int kPwT = 1;            // 32 output rows per workgroup
 constexpr int kPwXS = 16 + 4;      // words per LDS position: 16 channel pairs + pad (16-B rows)
+// Waves per SIMD the pointwise and the stem kernel are compiled for, by the pieces they keep
+// (DESIGN §30 has the resource report behind each value).  1 asks for nothing, as before: the
+// pointwise kernel reaches 6 / 7 / 8 waves on its own (64 / 56 / 40 registers), and the stem's
+// three-piece form stays the parent's (152 + 48 registers, 46 KB of LDS: 2 waves).  The stem's
+// reduced forms fit one more wave each without a spill: 134 registers and 31 KB (3), 114 and 15 KB (4).
+constexpr int front_waves(int np) { return 1; }
+constexpr int stem_waves(int np) { return np == 1 ? 4 : np == 2 ? 3 : 1; }
 
 struct FrontArgs {
     const float *in;
@@ -67,7 +74,8 @@ struct FrontArgs {
 // a copy of it for T = 1 that writes a channel window.  The two stay separate because either one
 // compiled from a shared function came out as different machine code; a change to
 // one is a change to both, and enc_finalize_kernel reads what both write.
-template <int T, bool STATS>
+// NP: the pieces the kernel kept; a one-piece kernel (bf16) has no acs and its result is acc alone.
+template <int T, bool STATS, int NP = 3>
 __device__ __forceinline__ void front_epilogue(const FrontArgs &g, const f32x4 (&acc)[T][2], const f32x4 (&acs)[T][2],
                                                int b, int tl, int y0, int x0, float *red) {
     constexpr int R = 32 * T;  // output rows per workgroup
@@ -89,7 +97,7 @@ __device__ __forceinline__ void front_epilogue(const FrontArgs &g, const f32x4 (
             float v[2];
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                v[c] = split_sum(acc[t][c][r], acs[t][c][r]) + bs;
+                v[c] = (NP == 1 ? acc[t][c][r] : split_sum(acc[t][c][r], acs[t][c][r])) + bs;
                 if (ok[c] && live) g.out[((size_t)b * g.cout + row) * HWo + (size_t)(y0 + j0 + c) * Wo + x] = v[c];
             }
             if constexpr (STATS) {
@@ -155,9 +163,11 @@ constexpr int stem_tap_offset(int tap) {  // the window offset of a tap (the zer
     return (t / kStemK) * kStemPW + t % kStemK;
 }
 
-template <bool STATS>
-__global__ __launch_bounds__(kNT) void stem_kernel(FrontArgs g) {
-    __shared__ __attribute__((aligned(16))) unsigned xs[3][kStemNPOS][kStemXS];
+// NP: the pieces kept per operand (3 = bf16x6, 2 = bf16x3, 1 = bf16: products<NP>, corr_bf16x6.h);
+// a reduced mode stages and fetches only those, from the same pack.
+template <bool STATS, int NP = 3>
+__global__ __launch_bounds__(kNT, stem_waves(NP)) void stem_kernel(FrontArgs g) {
+    __shared__ __attribute__((aligned(16))) unsigned xs[NP][kStemNPOS][kStemXS];
     __shared__ float red[STATS ? 2 * 32 * kStemT * 2 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int H = g.H, W = g.W, cin = g.cin;
@@ -168,15 +178,15 @@ __global__ __launch_bounds__(kNT) void stem_kernel(FrontArgs g) {
 
     // ---- A fragments of row blocks ob0, ob0 + 1, two steps ahead ----
     const int ob0 = (int)blockIdx.y * (2 * kStemT) + kStemT * (w & 1);
-    auto load_a = [&](u32x4 (&wa)[kStemT][3], int s) {
+    auto load_a = [&](u32x4 (&wa)[kStemT][NP], int s) {
 #pragma unroll
         for (int t = 0; t < kStemT; ++t) {
             const size_t base = ((size_t)(ob0 + t) * kStemSteps + s) * 3 * 64 + lane;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) wa[t][p] = g.frag[base + 64 * p];
+            for (int p = 0; p < NP; ++p) wa[t][p] = g.frag[base + 64 * p];
         }
     };
-    u32x4 wa[3][kStemT][3];
+    u32x4 wa[3][kStemT][NP];
     load_a(wa[0], 0);
     load_a(wa[1], 1);
 
@@ -207,8 +217,8 @@ __global__ __launch_bounds__(kNT) void stem_kernel(FrontArgs g) {
             split3((in_a >> i) & 1 ? v[i][0] : 0.f, (in_b >> i) & 1 ? v[i][1] : 0.f, hi, mid, lo);
             if (i + 1 < kStemNLD || idx < kStemWords) {
                 xs[0][ps][kp] = hi;
-                xs[1][ps][kp] = mid;
-                xs[2][ps][kp] = lo;
+                if constexpr (NP > 1) xs[1][ps][kp] = mid;
+                if constexpr (NP > 2) xs[2][ps][kp] = lo;
             }
         }
     }
@@ -228,18 +238,18 @@ __global__ __launch_bounds__(kNT) void stem_kernel(FrontArgs g) {
     for (int s = 0; s < kStemSteps; ++s) {
         if (s + 2 < kStemSteps) load_a(wa[(s + 2) % 3], s + 2);
         const int tp = odd ? stem_tap_offset(2 * s + 1) : stem_tap_offset(2 * s);
-        u32x4 xb[2][3];
+        u32x4 xb[2][NP];
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
+            for (int p = 0; p < NP; ++p)
                 xb[c][p] = *reinterpret_cast<const u32x4 *>(xb0 + (p * kStemNPOS + 2 * c * kStemPW + tp) * kStemXS);
 #pragma unroll
         for (int t = 0; t < kStemT; ++t)
 #pragma unroll
-            for (int c = 0; c < 2; ++c) six(wa[s % 3][t], xb[c], acc[t][c], acs[t][c]);
+            for (int c = 0; c < 2; ++c) products<NP>(wa[s % 3][t], xb[c], acc[t][c], acs[t][c]);
     }
-    front_epilogue<kStemT, STATS>(g, acc, acs, b, tl, y0, x0, red);
+    front_epilogue<kStemT, STATS, NP>(g, acc, acs, b, tl, y0, x0, red);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -260,9 +270,9 @@ __global__ __launch_bounds__(64) void pw_pack_kernel(const float *__restrict__ w
     store_pieces(dst, h, m, lo);
 }
 
-template <int S, bool STATS>
-__global__ __launch_bounds__(kNT) void pw_kernel(FrontArgs g) {
-    __shared__ __attribute__((aligned(16))) unsigned xs[3][kTH * kTW][kPwXS];
+template <int S, bool STATS, int NP = 3>
+__global__ __launch_bounds__(kNT, front_waves(NP)) void pw_kernel(FrontArgs g) {
+    __shared__ __attribute__((aligned(16))) unsigned xs[NP][kTH * kTW][kPwXS];
     __shared__ float red[STATS ? 2 * 32 * kPwT * 2 : 1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const size_t HW = (size_t)g.H * g.W;
@@ -285,12 +295,12 @@ __global__ __launch_bounds__(kNT) void pw_kernel(FrontArgs g) {
         }
     };
     const int ob0 = (int)blockIdx.y * (2 * kPwT) + kPwT * (w & 1);
-    auto load_a = [&](u32x4 (&wa)[kPwT][3], int ch) {
+    auto load_a = [&](u32x4 (&wa)[kPwT][NP], int ch) {
 #pragma unroll
         for (int t = 0; t < kPwT; ++t) {
             const size_t base = ((size_t)(ob0 + t) * NC + ch) * 3 * 64 + lane;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) wa[t][p] = g.frag[base + 64 * p];
+            for (int p = 0; p < NP; ++p) wa[t][p] = g.frag[base + 64 * p];
         }
     };
 
@@ -301,7 +311,7 @@ __global__ __launch_bounds__(kNT) void pw_kernel(FrontArgs g) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) acc[t][c] = acs[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     float va[4][2];
-    u32x4 wn[kPwT][3];
+    u32x4 wn[kPwT][NP];
     load_chunk(0, va);
     load_a(wn, 0);
 #pragma unroll 1
@@ -311,30 +321,30 @@ __global__ __launch_bounds__(kNT) void pw_kernel(FrontArgs g) {
             unsigned hi, mid, lo;
             split3(va[i][0], va[i][1], hi, mid, lo);
             xs[0][lane][wu + 4 * i] = hi;
-            xs[1][lane][wu + 4 * i] = mid;
-            xs[2][lane][wu + 4 * i] = lo;
+            if constexpr (NP > 1) xs[1][lane][wu + 4 * i] = mid;
+            if constexpr (NP > 2) xs[2][lane][wu + 4 * i] = lo;
         }
-        u32x4 wa[kPwT][3];
+        u32x4 wa[kPwT][NP];
 #pragma unroll
         for (int t = 0; t < kPwT; ++t)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) wa[t][p] = wn[t][p];
+            for (int p = 0; p < NP; ++p) wa[t][p] = wn[t][p];
         __syncthreads();
         const int nx = ch + 1 < NC ? ch + 1 : NC - 1;  // (past the end: a harmless re-read)
         load_chunk(nx, va);
         load_a(wn, nx);
-        u32x4 xb[2][3];
+        u32x4 xb[2][NP];
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) xb[c][p] = *reinterpret_cast<const u32x4 *>(&xs[p][(j0 + c) * kTW + fr][fk]);
+            for (int p = 0; p < NP; ++p) xb[c][p] = *reinterpret_cast<const u32x4 *>(&xs[p][(j0 + c) * kTW + fr][fk]);
 #pragma unroll
         for (int t = 0; t < kPwT; ++t)
 #pragma unroll
-            for (int c = 0; c < 2; ++c) six(wa[t], xb[c], acc[t][c], acs[t][c]);
+            for (int c = 0; c < 2; ++c) products<NP>(wa[t], xb[c], acc[t][c], acs[t][c]);
         __syncthreads();
     }
-    front_epilogue<kPwT, STATS>(g, acc, acs, b, tl, y0, x0, red);
+    front_epilogue<kPwT, STATS, NP>(g, acc, acs, b, tl, y0, x0, red);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -394,15 +404,36 @@ hipError_t launch_enc_stem_pack(const float *w, int cout, int cin, void *packed,
     return hipGetLastError();
 }
 
+namespace {
+template <int NP>
+void launch_stem_np(const FrontArgs &g, dim3 grid, hipStream_t s) {
+    if (g.stats)
+        hipLaunchKernelGGL((stem_kernel<true, NP>), grid, dim3(kNT), 0, s, g);
+    else
+        hipLaunchKernelGGL((stem_kernel<false, NP>), grid, dim3(kNT), 0, s, g);
+}
+
+template <int NP>
+void launch_pw_np(const FrontArgs &g, int stride, dim3 grid, hipStream_t s) {
+    switch ((stride == 2 ? 2 : 0) | (g.stats ? 1 : 0)) {
+        case 0: hipLaunchKernelGGL((pw_kernel<1, false, NP>), grid, dim3(kNT), 0, s, g); break;
+        case 1: hipLaunchKernelGGL((pw_kernel<1, true, NP>), grid, dim3(kNT), 0, s, g); break;
+        case 2: hipLaunchKernelGGL((pw_kernel<2, false, NP>), grid, dim3(kNT), 0, s, g); break;
+        default: hipLaunchKernelGGL((pw_kernel<2, true, NP>), grid, dim3(kNT), 0, s, g); break;
+    }
+}
+}  // namespace
+
 hipError_t launch_enc_stem(const float *in, int cin, int B, int H, int W, const void *packed, const float *bias,
-                           int cout, float *out, float *stats, hipStream_t s) {
-    if (!enc_stem_supported(cout, cin)) return hipErrorInvalidValue;
+                           int cout, float *out, float *stats, hipStream_t s, int precision) {
+    if (!enc_stem_supported(cout, cin) || !precision_supported(precision)) return hipErrorInvalidValue;
     const FrontArgs g = front_args(in, cin, B, H, W, 2, packed, bias, cout, out, stats);
     const dim3 grid((unsigned)B * g.tx * g.ty, (cout + 32 * kStemT - 1) / (32 * kStemT));
-    if (stats)
-        hipLaunchKernelGGL(stem_kernel<true>, grid, dim3(kNT), 0, s, g);
-    else
-        hipLaunchKernelGGL(stem_kernel<false>, grid, dim3(kNT), 0, s, g);
+    switch (precision) {
+        case 1: launch_stem_np<2>(g, grid, s); break;
+        case 2: launch_stem_np<1>(g, grid, s); break;
+        default: launch_stem_np<3>(g, grid, s); break;
+    }
     return hipGetLastError();
 }
 
@@ -422,15 +453,15 @@ hipError_t launch_enc_pw_pack(const float *w, int cout, int cin, void *packed, h
 }
 
 hipError_t launch_enc_pw(const float *in, int cin, int B, int H, int W, int stride, const void *packed,
-                         const float *bias, int cout, float *out, float *stats, hipStream_t s) {
-    if (!enc_pw_supported(cout, cin) || (stride != 1 && stride != 2)) return hipErrorInvalidValue;
+                         const float *bias, int cout, float *out, float *stats, hipStream_t s, int precision) {
+    if (!enc_pw_supported(cout, cin) || (stride != 1 && stride != 2) || !precision_supported(precision))
+        return hipErrorInvalidValue;
     const FrontArgs g = front_args(in, cin, B, H, W, stride, packed, bias, cout, out, stats);
     const dim3 grid((unsigned)B * g.tx * g.ty, (cout + 32 * kPwT - 1) / (32 * kPwT));
-    switch ((stride == 2 ? 2 : 0) | (stats ? 1 : 0)) {
-        case 0: hipLaunchKernelGGL((pw_kernel<1, false>), grid, dim3(kNT), 0, s, g); break;
-        case 1: hipLaunchKernelGGL((pw_kernel<1, true>), grid, dim3(kNT), 0, s, g); break;
-        case 2: hipLaunchKernelGGL((pw_kernel<2, false>), grid, dim3(kNT), 0, s, g); break;
-        default: hipLaunchKernelGGL((pw_kernel<2, true>), grid, dim3(kNT), 0, s, g); break;
+    switch (precision) {
+        case 1: launch_pw_np<2>(g, stride, grid, s); break;
+        case 2: launch_pw_np<1>(g, stride, grid, s); break;
+        default: launch_pw_np<3>(g, stride, grid, s); break;
     }
     return hipGetLastError();
 }

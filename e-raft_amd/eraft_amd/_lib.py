@@ -45,6 +45,8 @@ EXPORTS = ("corr_version", "corr_last_error", "corr_build", "corr_lookup", "corr
 # include/corr_mi355x_train.h: the sequence loss, alone and fused with the convex upsampling
 TRAIN_EXPORTS = ("corr_upsample_loss_workspace", "corr_upsample_loss", "corr_upsample_loss_bwd",
                  "corr_sequence_loss_workspace", "corr_sequence_loss", "corr_sequence_loss_bwd")
+# include/corr_mi355x_enc_prec.h: the encoders' convolutions in a precision mode
+ENC_PREC_EXPORTS = ("corr_enc_conv_forward_prec", "corr_enc_stem_forward_prec", "corr_enc_pw_forward_prec")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -185,6 +187,9 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_flow_head_weights_bytes.argtypes, lib.corr_flow_head_weights_bytes.restype = [], sz
     lib.corr_flow_head_pack_weights.argtypes = [vp, vp, vp]
     lib.corr_flow_head_forward.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.corr_enc_conv_forward_prec.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, sz, i, vp]
+    lib.corr_enc_stem_forward_prec.argtypes = [vp, i, i, i, i, vp, vp, i, vp, vp, sz, i, vp]
+    lib.corr_enc_pw_forward_prec.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, sz, i, vp]
     fl = ctypes.c_float
     lib.corr_upsample_loss_workspace.argtypes, lib.corr_upsample_loss_workspace.restype = [i, i, i], sz
     lib.corr_upsample_loss.argtypes = [vp, vp, vp, vp, i, i, i, i, i, fl, i, vp, vp, sz, vp]
@@ -193,7 +198,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_sequence_loss.argtypes = [vp, vp, vp, i, i, i, fl, i, vp, vp, sz, vp]
     lib.corr_sequence_loss_bwd.argtypes = [vp, vp, vp, vp, i, i, i, fl, vp, vp]
     for f in ("corr_upsample_loss", "corr_upsample_loss_bwd", "corr_sequence_loss", "corr_sequence_loss_bwd",
-              "corr_gru_half_step_prec", "corr_conv_forward_prec"):
+              "corr_gru_half_step_prec", "corr_conv_forward_prec", *ENC_PREC_EXPORTS):
         getattr(lib, f).restype = i
     for f in ("corr_ondemand_lookup_conv", "corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
               "corr_flow_head_forward", "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
@@ -1068,11 +1073,12 @@ def _enc_norm(scale, shift, B, C, device, name):
     return sp, hp, int(scale.dim() == 2)
 
 
-def enc_conv_forward(x, packed, bias, cout, stride=1, in_scale=None, in_shift=None, stats=False):
-    """corr_enc_conv_forward: the 3x3 convolution (padding 1, stride 1 or 2, + bias, no ReLU) of
+def enc_conv_forward(x, packed, bias, cout, stride=1, in_scale=None, in_shift=None, stats=False, precision=0):
+    """corr_enc_conv_forward_prec: the 3x3 convolution (padding 1, stride 1 or 2, + bias, no ReLU) of
     x [B, cin, H, W], or of relu(x * in_scale + in_shift) when the pair ([B, cin] or [cin]) is
     given, with the pack of conv_pack_weights.  Returns out [B, cout, Ho, Wo], or (out, stats) with
-    the per-tile statistics buffer for enc_norm_finalize when `stats`."""
+    the per-tile statistics buffer for enc_norm_finalize when `stats`.  precision is a CORR_PREC_*
+    value (precision.py; 0 = bf16x6 is corr_enc_conv_forward itself, bit for bit)."""
     xp = _dev(x, "x")
     if x.dim() != 4:
         raise ValueError(f"x must be [B, cin, H, W] (got {tuple(x.shape)})")
@@ -1094,8 +1100,9 @@ def enc_conv_forward(x, packed, bias, cout, stride=1, in_scale=None, in_shift=No
         nst = lib.corr_enc_stats_bytes(B, cout, Ho, Wo)
         st = torch.empty(nst // 4, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _check(lib.corr_enc_conv_forward(xp, cin, B, H, W, stride, sp, hp, nb, pk, biasp, cout, out.data_ptr(),
-                                         None if st is None else st.data_ptr(), nst, _stream(x)))
+        _check(lib.corr_enc_conv_forward_prec(xp, cin, B, H, W, stride, sp, hp, nb, pk, biasp, cout, out.data_ptr(),
+                                              None if st is None else st.data_ptr(), nst, int(precision),
+                                              _stream(x)))
     return (out, st) if stats else out
 
 
@@ -1156,7 +1163,7 @@ def enc_pw_pack_weights(w):
     return _enc_front_pack(w, 1, "pw")
 
 
-def _enc_front_forward(name, x, packed, bias, cout, stride, stats):
+def _enc_front_forward(name, x, packed, bias, cout, stride, stats, precision):
     xp = _dev(x, "x")
     if x.dim() != 4:
         raise ValueError(f"x must be [B, cin, H, W] (got {tuple(x.shape)})")
@@ -1177,25 +1184,28 @@ def _enc_front_forward(name, x, packed, bias, cout, stride, stats):
     stp = None if st is None else st.data_ptr()
     with torch.cuda.device(x.device):
         if name == "stem":
-            _check(lib.corr_enc_stem_forward(xp, cin, B, H, W, pk, biasp, cout, out.data_ptr(), stp, nst, _stream(x)))
+            _check(lib.corr_enc_stem_forward_prec(xp, cin, B, H, W, pk, biasp, cout, out.data_ptr(), stp, nst,
+                                                  int(precision), _stream(x)))
         else:
-            _check(lib.corr_enc_pw_forward(xp, cin, B, H, W, stride, pk, biasp, cout, out.data_ptr(), stp, nst,
-                                           _stream(x)))
+            _check(lib.corr_enc_pw_forward_prec(xp, cin, B, H, W, stride, pk, biasp, cout, out.data_ptr(), stp, nst,
+                                                int(precision), _stream(x)))
     return (out, st) if stats else out
 
 
-def enc_stem_forward(x, packed, bias, cout, stats=False):
-    """corr_enc_stem_forward: the 7x7 convolution (stride 2, padding 3, + bias, no ReLU) of
+def enc_stem_forward(x, packed, bias, cout, stats=False, precision=0):
+    """corr_enc_stem_forward_prec: the 7x7 convolution (stride 2, padding 3, + bias, no ReLU) of
     x [B, cin, H, W], cin <= 16, with the pack of enc_stem_pack_weights.  Returns out
-    [B, cout, Ho, Wo], or (out, stats) with the per-tile statistics for enc_norm_finalize."""
-    return _enc_front_forward("stem", x, packed, bias, cout, 2, stats)
+    [B, cout, Ho, Wo], or (out, stats) with the per-tile statistics for enc_norm_finalize.
+    precision: a CORR_PREC_* value (0 = bf16x6 is corr_enc_stem_forward itself, bit for bit)."""
+    return _enc_front_forward("stem", x, packed, bias, cout, 2, stats, precision)
 
 
-def enc_pw_forward(x, packed, bias, cout, stride=1, stats=False):
-    """corr_enc_pw_forward: the 1x1 convolution (stride 1 or 2, + bias, no ReLU) of
+def enc_pw_forward(x, packed, bias, cout, stride=1, stats=False, precision=0):
+    """corr_enc_pw_forward_prec: the 1x1 convolution (stride 1 or 2, + bias, no ReLU) of
     x [B, cin, H, W] with the pack of enc_pw_pack_weights.  Returns out [B, cout, Ho, Wo], or
-    (out, stats) with the per-tile statistics for enc_norm_finalize."""
-    return _enc_front_forward("pw", x, packed, bias, cout, stride, stats)
+    (out, stats) with the per-tile statistics for enc_norm_finalize.
+    precision: a CORR_PREC_* value (0 = bf16x6 is corr_enc_pw_forward itself, bit for bit)."""
+    return _enc_front_forward("pw", x, packed, bias, cout, stride, stats, precision)
 
 
 def enc_join_affine(y, scale, shift, skip, skip_scale=None, skip_shift=None, skip_relu=False, out=None):

@@ -8,6 +8,8 @@ input; corr_enc_join does the same for the block's output and adds the skip, and
 corr_enc_join_affine also normalises that skip (the raw stem map with its ReLU, the raw projection
 without one).  An eval-mode batch norm brings its scale and shift from its running statistics
 instead.  USE_KERNEL says which pieces take a kernel; the others run on torch as they always did.
+module.precision (precision.py: "bf16x6", "bf16x3" or "bf16") is the mode of every convolution that
+takes a kernel; a piece on torch stays fp32.
 Inference only: there is no backward, so model.BasicEncoder takes this path only when autograd is
 not recording.
 """
@@ -16,7 +18,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, precision
 from ._cache import cached
 from .update import _conv_pack
 
@@ -66,39 +68,42 @@ def _norm_of(y, st, norm, instance):
     return _lib.enc_norm_finalize(st, y.shape[0], y.shape[1], y.shape[2], y.shape[3], norm.eps)
 
 
-def _conv_norm(key, conv, norm, x, in_norm, instance):
+def _conv_norm(key, conv, norm, x, in_norm, instance, prec=0):
     """relu(norm(conv(n(x)))) as (y, scale, shift) with the result relu(y * scale + shift) left to
     the consumer, or as (result, None, None) when the convolution runs on torch.  n(x) is
-    relu(x * in_norm[0] + in_norm[1]), or x when in_norm is None."""
+    relu(x * in_norm[0] + in_norm[1]), or x when in_norm is None.  prec: the kernel's CORR_PREC_* mode."""
     if not USE_KERNEL[key]:
         return F.relu(norm(conv(x if in_norm is None else _affine(x, *in_norm)))), None, None
     packed, bias = _conv_pack((conv,))
     sc, sh = in_norm if in_norm is not None else (None, None)
     if not instance:
-        return (_lib.enc_conv_forward(x, packed, bias, conv.out_channels, conv.stride[0], sc, sh), *_bn_affine(norm))
-    y, st = _lib.enc_conv_forward(x, packed, bias, conv.out_channels, conv.stride[0], sc, sh, stats=True)
+        return (_lib.enc_conv_forward(x, packed, bias, conv.out_channels, conv.stride[0], sc, sh, precision=prec),
+                *_bn_affine(norm))
+    y, st = _lib.enc_conv_forward(x, packed, bias, conv.out_channels, conv.stride[0], sc, sh, stats=True,
+                                  precision=prec)
     return (y, *_norm_of(y, st, norm, True))
 
 
-def _pw(conv, x, stats=False):
-    """conv(x) for a 1x1 Conv2d on the pointwise kernel (with the statistics when asked)."""
+def _pw(conv, x, stats=False, prec=0):
+    """conv(x) for a 1x1 Conv2d on the pointwise kernel (with the statistics when asked) in the
+    CORR_PREC_* mode prec."""
     packed, bias = _front_pack(conv, _lib.enc_pw_pack_weights)
-    return _lib.enc_pw_forward(x, packed, bias, conv.out_channels, conv.stride[0], stats=stats)
+    return _lib.enc_pw_forward(x, packed, bias, conv.out_channels, conv.stride[0], stats=stats, precision=prec)
 
 
-def _block(name, block, x, x_norm, instance):
+def _block(name, block, x, x_norm, instance, prec):
     """ResidualBlock.forward (extractor.py:43-52) for `block` on relu(x * x_norm[0] + x_norm[1])
     (the raw stem map and its norm), or on x when x_norm is None."""
     s2 = block.downsample is not None
-    y, sc, sh = _conv_norm(name + ".s2" if s2 else name, block.conv1, block.norm1, x, x_norm, instance)
-    y, sc, sh = _conv_norm(name, block.conv2, block.norm2, y, None if sc is None else (sc, sh), instance)
+    y, sc, sh = _conv_norm(name + ".s2" if s2 else name, block.conv1, block.norm1, x, x_norm, instance, prec)
+    y, sc, sh = _conv_norm(name, block.conv2, block.norm2, y, None if sc is None else (sc, sh), instance, prec)
     if sc is None:  # conv2 ran on torch: y is normalised already, the join is torch's
         if x_norm is not None:
             x = _affine(x, *x_norm)
         return F.relu((block.downsample(x) if s2 else x) + y)
     if s2 and USE_KERNEL[name + ".proj"]:
         conv, norm = block.downsample[0], block.downsample[1]
-        p = _pw(conv, x, stats=instance)
+        p = _pw(conv, x, stats=instance, prec=prec)
         p, st = p if instance else (p, None)
         return _lib.enc_join_affine(y, sc, sh, p, *_norm_of(p, st, norm, instance), skip_relu=False, out=y)
     if s2:
@@ -115,15 +120,16 @@ def encoder_forward(module, x):
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
         raise RuntimeError("x must be a tensor on an MI355X (HIP) device: eraft_amd has no CPU fallback")
     instance = module.norm_fn == "instance"
+    prec = precision.code(module.precision)
     x, x_norm = x.detach().contiguous(), None
     if USE_KERNEL["stem"] and x.shape[1] <= STEM_MAX_CIN:
         packed, bias = _front_pack(module.conv1, _lib.enc_stem_pack_weights)
-        y = _lib.enc_stem_forward(x, packed, bias, module.conv1.out_channels, stats=instance)
+        y = _lib.enc_stem_forward(x, packed, bias, module.conv1.out_channels, stats=instance, precision=prec)
         x, st = y if instance else (y, None)
         x_norm = _norm_of(x, st, module.norm1, instance)
     else:
         x = F.relu(module.norm1(module.conv1(x))).contiguous()
     for name in ("layer1", "layer2", "layer3"):
         for block in getattr(module, name):
-            x, x_norm = _block(name, block, x, x_norm, instance), None
-    return _pw(module.conv2, x) if USE_KERNEL["head"] else module.conv2(x)
+            x, x_norm = _block(name, block, x, x_norm, instance, prec), None
+    return _pw(module.conv2, x, prec=prec) if USE_KERNEL["head"] else module.conv2(x)

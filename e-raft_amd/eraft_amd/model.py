@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from .corr import CorrBlock
 from .ondemand import OnDemandConvCorrBlock, OnDemandCorrBlock
-from .precision import DEFAULT as _PRECISION, resolve as _resolve_precision
+from .precision import DEFAULT as _PRECISION, resolve as _resolve_precision, resolve_encoder as _resolve_encoder_precision
 from .utils import coords_grid
 
 
@@ -90,6 +90,9 @@ class BasicEncoder(nn.Module):
     # block's join, instead of MIOpen / rocBLAS convolutions and torch norm / ReLU / add kernels.
     # Default off (DESIGN §16 and §18 have the measurements); training always runs the torch code.
     fused = os.environ.get("ERAFT_AMD_FUSE_ENCODER", "0") == "1"
+    # The fused convolutions' precision mode (precision.py); ERAFT sets it on its two encoders.  The
+    # torch path ignores it.
+    precision = _PRECISION
 
     def _fusable(self, x):
         """encoder.encoder_forward is built for an fp32 GPU tensor, instance norm or eval-mode
@@ -357,8 +360,10 @@ class ERAFT(nn.Module):
     # has the measurements).
     fuse_ondemand_conv = os.environ.get("ERAFT_AMD_ONDEMAND_FUSE_CONV", "0") == "1"
     # The precision mode of the GRU and the update block's 3x3 convolutions ("bf16x6", "bf16x3" or
-    # "bf16": precision.py); an instance takes it from its config (below).
+    # "bf16": precision.py), and that of the two encoders' convolutions; an instance takes each from
+    # its config (below).
     precision = _PRECISION
+    encoder_precision = _PRECISION
 
     def __init__(self, config, n_first_channels):
         super().__init__()
@@ -378,12 +383,21 @@ class ERAFT(nn.Module):
         self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn="batch", dropout=0,
                                  n_first_channels=n_first_channels)
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=hdim)
-        # The reference's switch: config key `mixed_precision` (absent / False: "bf16x6", every
-        # product exact as before; True: "bf16x3"; or a mode's name), ERAFT_AMD_PRECISION=<name>
-        # overrides it.  It acts only where the fused kernels run (ERAFT_AMD_FUSE_GRU=1 /
-        # ERAFT_AMD_FUSE_UPDATE=1 at inference); the torch paths and training stay fp32.
+        # The reference's switch (model/eraft.py:102-133 puts fnet, cnet and the update block under
+        # one autocast) is two knobs here, and setting both corresponds to it:
+        #   `mixed_precision` (absent / False: "bf16x6", every product exact as before; True:
+        #   "bf16x3"; or a mode's name), overridden by ERAFT_AMD_PRECISION=<name>, reaches the GRU's
+        #   eight convolutions and the update block's convc2, convf2, conv and the two heads' first
+        #   convolutions, where their fused kernels run (ERAFT_AMD_FUSE_GRU=1 / ERAFT_AMD_FUSE_UPDATE=1);
+        #   `encoder_precision` (the same values), overridden by ERAFT_AMD_ENCODER_PRECISION=<name>,
+        #   reaches the 16 convolutions of fnet and the 16 of cnet (stem, 3x3 stages, 1x1 projections
+        #   and head), where encoder.encoder_forward runs (ERAFT_AMD_FUSE_ENCODER=1).
+        # Both act at inference only; the torch paths and training stay fp32.  convf1, the flow
+        # head's second convolution, the mask head and the lookup with convc1 stay "bf16x6".
         self.precision = _resolve_precision(config)
         self.update_block.precision = self.update_block.gru.precision = self.precision
+        self.encoder_precision = _resolve_encoder_precision(config)
+        self.fnet.precision = self.cnet.precision = self.encoder_precision
 
     def freeze_bn(self):
         for m in self.modules():

@@ -1,17 +1,28 @@
-"""The precision modes of the per-iteration kernels (include/corr_mi355x.h: CORR_PREC_*), the
+"""The precision modes of the convolution kernels (include/corr_mi355x.h: CORR_PREC_*), the
 counterpart of the reference's mixed_precision (model/eraft.py:31,102-133).
 
-A mode names the pieces of the exact three-piece bf16 split that the fused GRU half step and the
-update block's fused 3x3 convolutions keep of both operands:
+A mode names the pieces of the exact three-piece bf16 split that a kernel keeps of both operands:
 
   "bf16x6"  hi, mid, lo: six products per fp32 product, no narrower than fp32 (the default)
   "bf16x3"  hi, mid: three products, operands to 2^-18 and the dropped mid x mid to 2^-16 relative
   "bf16"    hi: one product, operands to 2^-9 relative
 
-Accumulation is fp32 in every mode.  The mode acts only where those kernels run (inference with
-ERAFT_AMD_FUSE_GRU=1 / ERAFT_AMD_FUSE_UPDATE=1): the torch paths and training stay fp32 and ignore
-it, and convf1, the flow head's second convolution, the mask head with the upsampling, the lookup
-with convc1 and the encoders stay "bf16x6" by design.
+Accumulation is fp32 in every mode.  Two knobs choose a mode, each for its own layers:
+
+  `mixed_precision` / ERAFT_AMD_PRECISION (resolve)
+      the fused GRU half steps (the eight convolutions of SepConvGRU) and the update block's fused
+      3x3 convolutions (convc2, convf2, conv, the flow head's and the mask head's first), where those
+      kernels run: inference with ERAFT_AMD_FUSE_GRU=1 / ERAFT_AMD_FUSE_UPDATE=1.
+  `encoder_precision` / ERAFT_AMD_ENCODER_PRECISION (resolve_encoder)
+      the 32 convolutions of fnet and cnet (each: the 7x7 stem, the twelve 3x3 convolutions of the
+      residual stages, the two 1x1 projections and the 1x1 head), where encoder.encoder_forward runs:
+      inference with ERAFT_AMD_FUSE_ENCODER=1 on fp32 GPU tensors.  A piece that encoder.USE_KERNEL
+      leaves on torch stays fp32.
+
+The reference's single switch wraps the encoders and the update block in one autocast, so it
+corresponds to setting both.  The torch paths and training stay fp32 and ignore both; convf1, the
+flow head's second convolution, the mask head with the upsampling and the lookup with convc1 stay
+"bf16x6" under either.
 """
 from __future__ import annotations
 
@@ -21,6 +32,7 @@ BF16X6, BF16X3, BF16 = 0, 1, 2
 MODES = {"bf16x6": BF16X6, "bf16x3": BF16X3, "bf16": BF16}
 DEFAULT = "bf16x6"
 ENV = "ERAFT_AMD_PRECISION"
+ENCODER_ENV = "ERAFT_AMD_ENCODER_PRECISION"
 
 
 def code(name) -> int:
@@ -30,20 +42,32 @@ def code(name) -> int:
     return MODES[name]
 
 
-def resolve(config=None) -> str:
-    """The mode name a model runs in: the config key `mixed_precision` (absent or False: "bf16x6";
-    True: "bf16x3"; a string: that mode), overridden by ERAFT_AMD_PRECISION=<name>; a variable that is
-    set but empty counts as unset, any other unknown name raises."""
-    env = os.environ.get(ENV) or None
+def _resolve(config, key_name, env_name) -> str:
+    env = os.environ.get(env_name) or None
     if env is not None:
         name = env.lower()
     else:
-        key = config.get("mixed_precision", False) if hasattr(config, "get") else False
+        key = config.get(key_name, False) if hasattr(config, "get") else False
         if key is None or isinstance(key, bool):
             name = "bf16x3" if key else DEFAULT
         elif isinstance(key, str):
             name = key.lower()
         else:
-            raise ValueError(f"mixed_precision must be a bool or one of {sorted(MODES)} (got {key!r})")
+            raise ValueError(f"{key_name} must be a bool or one of {sorted(MODES)} (got {key!r})")
     code(name)
     return name
+
+
+def resolve(config=None) -> str:
+    """The mode name of a model's GRU and update block: the config key `mixed_precision` (absent or
+    False: "bf16x6"; True: "bf16x3"; a string: that mode), overridden by ERAFT_AMD_PRECISION=<name>; a
+    variable that is set but empty counts as unset, any other unknown name raises."""
+    return _resolve(config, "mixed_precision", ENV)
+
+
+def resolve_encoder(config=None) -> str:
+    """The mode name of a model's two encoders: the config key `encoder_precision` (absent, None or
+    False: "bf16x6"; True: "bf16x3"; a string: that mode), overridden by
+    ERAFT_AMD_ENCODER_PRECISION=<name>; a variable that is set but empty counts as unset, any other
+    unknown name raises.  Independent of `mixed_precision`."""
+    return _resolve(config, "encoder_precision", ENCODER_ENV)

@@ -2,7 +2,7 @@
 Every variant is captured as one HIP graph and replayed; the variants of a measurement are
 alternated in ONE process on the same inputs, so box-to-box spread drops out.
     python tools/bench_encoder.py [--sizes dsec,b8,hires1920] [--kinds layer1.first,stem,...] [--trials 5]
-                                  [--json profiles/encoder_bench.json]
+                                  [--precision bf16x3,bf16] [--json profiles/encoder_bench.json]
 Per size (the encoder's input; fnet sees both voxel grids as one batch, cnet one) and per encoder
 (fnet: instance norm, cnet: eval-mode batch norm):
   (a) each kind of convolution against the torch ops it replaces.  "first": a block's conv1 (at
@@ -21,7 +21,10 @@ Per size (the encoder's input; fnet sees both voxel grids as one batch, cnet one
       encoder.USE_KERNEL ("fused").
 Median / min / max ms per call over the trial windows; for (a) each path's norm-relative error
 against the same formula in fp64 on the GPU, for (b) the kernel path's norm-relative difference
-from the torch path (the parity against the reference is tests/test_encoder.py's).  Prints one JSON
+from the torch path (the parity against the reference is tests/test_encoder.py's).
+--precision adds, to every row of (a), the kernel side in each named mode ("kernel_<mode>", with its
+own error against fp64 and its time over the bf16x6 kernel's) and, to (b), the committed table in
+that mode ("fused_<mode>", module.precision), all in the same alternation.  Prints one JSON
 document; --json also writes it to a file."""
 import argparse
 import json
@@ -34,7 +37,7 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "e-raft_amd"))
-from eraft_amd import _lib, encoder  # noqa: E402
+from eraft_amd import _lib, encoder, precision  # noqa: E402
 from eraft_amd.model import BasicEncoder  # noqa: E402
 
 # name: (pairs per batch, C_in, H, W) of the model input
@@ -105,12 +108,13 @@ def alternate(graphs, trials, budget=0.15):
 
 
 def front_fns(m, kind, x, maps, instance):
-    """(torch_fn, kernel_fn, check, ref, src) of one of the FRONT rows."""
+    """(torch_fn, kernel_fn, check, ref, src) of one of the FRONT rows; kernel_fn(prec) runs in the
+    CORR_PREC_* mode prec."""
     if kind == "head":
         with torch.no_grad():
             src = m.layer3(maps["layer3"])
             ref = F.conv2d(src.double(), m.conv2.weight.double(), m.conv2.bias.double())
-        return (lambda: m.conv2(src)), (lambda: encoder._pw(m.conv2, src)), (lambda o: o), ref, src
+        return (lambda: m.conv2(src)), (lambda prec=0: encoder._pw(m.conv2, src, prec=prec)), (lambda o: o), ref, src
     if kind == "stem":
         src, conv, norm, relu = x, m.conv1, m.norm1, True
     else:
@@ -130,19 +134,19 @@ def front_fns(m, kind, x, maps, instance):
         s = norm(conv(src))
         return _lib.enc_join(y, sc, sh, F.relu(s) if relu else s)
 
-    def kernel_fn():
+    def kernel_fn(prec=0):
         if kind == "stem":
             packed, bias = encoder._front_pack(conv, _lib.enc_stem_pack_weights)
-            p = _lib.enc_stem_forward(src, packed, bias, conv.out_channels, stats=instance)
+            p = _lib.enc_stem_forward(src, packed, bias, conv.out_channels, stats=instance, precision=prec)
         else:
-            p = encoder._pw(conv, src, stats=instance)
+            p = encoder._pw(conv, src, stats=instance, prec=prec)
         p, st = p if instance else (p, None)
         return _lib.enc_join_affine(y, sc, sh, p, *encoder._norm_of(p, st, norm, instance), skip_relu=relu)
     return torch_fn, kernel_fn, (lambda o: o), ref, src
 
 
-def bench_encoder(m, x, which, trials, stream, kinds):
-    """(a) and (b) for one encoder `m` on the input x."""
+def bench_encoder(m, x, which, trials, stream, kinds, modes=()):
+    """(a) and (b) for one encoder `m` on the input x; modes: the reduced modes measured beside."""
     instance = m.norm_fn == "instance"
     res = {"norm": m.norm_fn, "B": x.shape[0], "convs": {}}
     with torch.no_grad():
@@ -162,8 +166,8 @@ def bench_encoder(m, x, which, trials, stream, kinds):
                 ref = F.relu(norm64(norm, conv64(conv, src)))
             torch_fn = lambda: F.relu(norm(conv(src)))
 
-            def kernel_fn():
-                y, sc, sh = encoder._conv_norm("on", conv, norm, src, None, instance)
+            def kernel_fn(prec=0):
+                y, sc, sh = encoder._conv_norm("on", conv, norm, src, None, instance, prec)
                 return y, sc, sh
             check = lambda o: encoder._affine(*o)
         else:
@@ -179,38 +183,48 @@ def bench_encoder(m, x, which, trials, stream, kinds):
                 ref = F.relu(skip.double() + F.relu(norm64(norm, conv64(conv, act))))
             torch_fn = lambda: F.relu(skip + F.relu(norm(conv(act))))
 
-            def kernel_fn():
-                y, sc, sh = encoder._conv_norm("on", conv, norm, src, (sc0, sh0), instance)
+            def kernel_fn(prec=0):
+                y, sc, sh = encoder._conv_norm("on", conv, norm, src, (sc0, sh0), instance, prec)
                 return _lib.enc_join(y, sc, sh, skip, out=y)
             check = lambda o: o
         gt, ot, kt = capture(torch_fn, stream)
         gk, ok, kk = capture(kernel_fn, stream)
-        r = alternate({"torch": gt, "kernel": gk}, trials)
+        reduced = {mode: capture(lambda mode=mode: kernel_fn(precision.code(mode)), stream) for mode in modes}
+        r = alternate(dict({"torch": gt, "kernel": gk}, **{f"kernel_{mode}": c[0] for mode, c in reduced.items()}), trials)
         r["shape_in"] = list(src.shape)
         r["cout"], r["stride"] = conv.out_channels, conv.stride[0]
         with torch.no_grad():
             r["kernel"]["rel_err_vs_fp64"] = norm_rel(check(ok), ref)
             r["torch"]["rel_err_vs_fp64"] = norm_rel(ot, ref)
+            for mode, c in reduced.items():
+                r[f"kernel_{mode}"]["rel_err_vs_fp64"] = norm_rel(check(c[1]), ref)
+                r[f"{mode}_over_bf16x6"] = round(r[f"kernel_{mode}"]["call_ms_median"] / r["kernel"]["call_ms_median"], 3)
         r["kernel_over_torch"] = round(r["kernel"]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
         res["convs"][kind] = r
-        del gt, gk, kt, kk, ot, ok, ref
+        del gt, gk, kt, kk, ot, ok, ref, reduced
         torch.cuda.empty_cache()
 
     table = {k: v for k, v in encoder.USE_KERNEL.items() if k != "on"}
     graphs, outs, keep = {}, {}, []
     stages = dict(table, **dict.fromkeys(FRONT, False))
-    for vname, on, tab in (("torch", False, table), ("stages", True, stages), ("all", True, dict.fromkeys(table, True)),
-                           ("fused", True, table)):
+    variants = [("torch", False, table, "bf16x6"), ("stages", True, stages, "bf16x6"),
+                ("all", True, dict.fromkeys(table, True), "bf16x6"), ("fused", True, table, "bf16x6")]
+    variants += [(f"fused_{mode}", True, table, mode) for mode in modes]
+    for vname, on, tab, mode in variants:
         BasicEncoder.fused = on
         encoder.USE_KERNEL.update(tab)
+        m.precision = mode
         graphs[vname], outs[vname], k = capture(lambda: m(x), stream)
         keep.append(k)
     BasicEncoder.fused = False
     encoder.USE_KERNEL.update(table)
+    m.precision = "bf16x6"
     r = alternate(graphs, trials)
-    for vname in ("stages", "all", "fused"):
+    for vname, _, _, _ in variants[1:]:
         r[vname]["vs_torch_rel"] = norm_rel(outs[vname], outs["torch"])
         r[f"{vname}_over_torch"] = round(r[vname]["call_ms_median"] / r["torch"]["call_ms_median"], 3)
+    for mode in modes:
+        r[f"{mode}_over_bf16x6"] = round(r[f"fused_{mode}"]["call_ms_median"] / r["fused"]["call_ms_median"], 3)
     r["use_kernel"] = table
     res["whole"] = r
     del graphs, keep, outs
@@ -218,7 +232,7 @@ def bench_encoder(m, x, which, trials, stream, kinds):
     return res
 
 
-def bench_size(name, trials, dev, kinds):
+def bench_size(name, trials, dev, kinds, modes=()):
     pairs, C, H, W = SIZES[name]
     torch.manual_seed(1234)
     stream = torch.cuda.Stream()
@@ -232,7 +246,7 @@ def bench_size(name, trials, dev, kinds):
                         mod.running_mean.normal_(0.0, 0.1)
                         mod.running_var.uniform_(0.5, 1.5)
         x = torch.randn(B, C, H, W, device=dev) * (torch.rand(B, C, H, W, device=dev) < 0.15)
-        res[which] = bench_encoder(m, x, which, trials, stream, kinds)
+        res[which] = bench_encoder(m, x, which, trials, stream, kinds, modes)
         del m, x
         torch.cuda.empty_cache()
     return res
@@ -243,6 +257,7 @@ def main():
     ap.add_argument("--sizes", default="dsec,b8,hires1920")
     ap.add_argument("--kinds", default=",".join(list(KINDS) + list(FRONT)), help="the rows of (a) to measure")
     ap.add_argument("--trials", type=int, default=5)
+    ap.add_argument("--precision", default="", help="reduced modes to measure beside bf16x6, e.g. bf16x3,bf16")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -252,12 +267,16 @@ def main():
     kinds = [k for k in a.kinds.split(",") if k]
     if any(k not in KINDS and k not in FRONT for k in kinds):
         sys.exit(f"--kinds must be among {list(KINDS) + list(FRONT)}")
+    modes = [p for p in a.precision.split(",") if p]
+    if any(p not in ("bf16x3", "bf16") for p in modes):
+        sys.exit("--precision must be among bf16x3, bf16")
     dev = torch.device("cuda", 0)
     encoder.USE_KERNEL["on"] = True  # the key the single-convolution measurements run under
     doc = {"device": torch.cuda.get_device_name(0),
            "call": "one HIP graph per variant, variants alternated; convs: kernel launches vs the torch ops they "
                    "replace; whole: BasicEncoder.forward",
-           "sizes": {n: bench_size(n, a.trials, dev, kinds) for n in a.sizes.split(",")}}
+           "precision": modes,
+           "sizes": {n: bench_size(n, a.trials, dev, kinds, modes) for n in a.sizes.split(",")}}
     del encoder.USE_KERNEL["on"]
     text = json.dumps(doc, indent=1)
     print(text)
