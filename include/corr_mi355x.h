@@ -423,8 +423,9 @@ int corr_lookup_conv(const float *const *pyr, const float *coords, int B, int H,
  * (hi * hi) accumulate in one fp32 register and the five smaller ones (lo*hi, hi*lo, mid*mid,
  * mid*hi, hi*mid, in that order) in a second; out = (first is infinite ? first : first + second) +
  * bias, then ReLU as torch's (a NaN stays a NaN).  Against relu(conv2d(lookup)) in fp64: within
- * 1e-5 of the largest output (measured ~2e-7).  A non-finite lookup value (NaN coordinates do
- * not give one; non-finite features may) reaches all 256 outputs of its query.  Deterministic:
+ * 1e-5 of the largest output (measured ~2e-7).  A non-finite lookup value (non-finite
+ * coordinates and one-cell levels give NaN, as in corr_ondemand_lookup; non-finite features may
+ * give one) reaches all 256 outputs of its query.  Deterministic:
  * no atomics, reruns are bit-identical.
  */
 int corr_ondemand_lookup_conv(const void *workspace, const float *coords, int B, int D, int H, int W, int levels,

@@ -88,3 +88,26 @@ def test_extra_makes_again():
     second = cached("t_extra", ts, "the value", make, extra=(1e-3,))
     assert second is not first and make.calls == 2
     assert cached("t_extra", ts, "the value", make, extra=(1e-3,)) is second and make.calls == 2
+
+
+def test_cpu_tensors_take_no_part_in_the_stream_ordering(monkeypatch):
+    """Off the GPU an entry keeps no stream and no event, and neither a make nor a hit asks torch.cuda
+    for anything (the ordering of a hit behind the make on another stream is tests/test_family_discipline.py's)."""
+    def refuse(*a, **k):
+        raise AssertionError("torch.cuda was asked about streams for CPU tensors")
+    for name in ("current_stream", "is_current_stream_capturing", "Event"):
+        monkeypatch.setattr(torch.cuda, name, refuse)
+    ts, make = _params(), _Make()
+    first = cached("t_cpu_streams", ts, "the value", make)
+    assert cached("t_cpu_streams", ts, "the value", make) is first and make.calls == 1
+    ent = _cache._ENTRIES[("t_cpu_streams",) + tuple(id(t) for t in ts)]
+    assert ent[2] is first and ent[3] is None
+
+
+def test_the_tensors_of_a_value():
+    """What a hit from another stream records the stream on: the value itself, or the tensors of a
+    (nested) tuple or list; anything else holds no device memory of its own."""
+    a, b = _params()
+    assert _cache._value_tensors(a) == (a,)
+    assert _cache._value_tensors((a, b)) == (a, b) and _cache._value_tensors([a, (b, a)]) == (a, b, a)
+    assert _cache._value_tensors(object()) == () and _cache._value_tensors((1.0, None)) == ()
