@@ -12,6 +12,7 @@
 
 #include "../../include/corr_mi355x_enc_prec.h"
 #include "../../include/corr_mi355x_train.h"
+#include "../../include/corr_mi355x_train_head.h"
 #include "corr_common.h"
 
 namespace corr {
@@ -1332,6 +1333,71 @@ int corr_sequence_loss_bwd(const float *pred, const float *gt, const float *vali
         (rc = check_ptr(fn, scale, "scale")) || (rc = check_ptr(fn, dpred, "dpred")))
         return rc;
     return hip_status(launch_sequence_loss_bwd(pred, gt, valid, scale, N, H, W, max_flow, dpred, (hipStream_t)stream),
+                      fn);
+}
+
+}  // extern "C"
+
+// ---- include/corr_mi355x_train_head.h: the same loss with the mask head inside the launch ----
+namespace corr {
+
+static int check_mask_loss(const char *fn, const float *hidden, int hidden_channels, int hidden_offset,
+                           const float *flow, const void *packed, const float *bias, float mask_scale,
+                           const float *gt, const float *valid, int N, int h, int w, int H, int W, float max_flow,
+                           const void *workspace, size_t workspace_bytes) {
+    // N*576*h*w < 2^31: dz, every pixel index and, by H*W <= 64 h*w, gt and valid
+    int rc = check_upsample_loss(fn, N, h, w, H, W, max_flow);
+    if (rc) return rc;
+    if ((rc = check_window(fn, "hidden_offset", hidden_offset, 256, "hidden_channels", hidden_channels))) return rc;
+    if ((long double)N * hidden_channels * h * w >= (long double)(1LL << 31))
+        return fail(CORR_EINVAL, "%s: N*hidden_channels*h*w too large (2^31 elements or more)", fn);
+    if (!(mask_scale - mask_scale == 0.f)) return fail(CORR_EINVAL, "%s: mask_scale must be finite", fn);
+    if ((rc = check_ptr(fn, hidden, "hidden")) || (rc = check_ptr(fn, flow, "flow")) ||
+        (rc = check_packed(fn, packed)) || (rc = check_ptr(fn, bias, "bias")) || (rc = check_ptr(fn, gt, "gt")) ||
+        (rc = check_ptr(fn, valid, "valid")))
+        return rc;
+    return check_workspace8(fn, workspace, workspace_bytes, mask_upsample_loss_workspace(N, h, w));
+}
+
+}  // namespace corr
+
+extern "C" {
+
+size_t corr_mask_upsample_loss_workspace(int N, int h, int w) {
+    if (N < 1 || h < 1 || w < 1) return 0;
+    return mask_upsample_loss_workspace(N, h, w);
+}
+
+int corr_mask_upsample_loss(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                            const void *packed, const float *bias, float mask_scale, const float *gt,
+                            const float *valid, int N, int h, int w, int H, int W, float max_flow, int want_metrics,
+                            double *out, void *workspace, size_t workspace_bytes, void *stream) {
+    static const char *fn = "corr_mask_upsample_loss";
+    g_err[0] = 0;
+    int rc = check_mask_loss(fn, hidden, hidden_channels, hidden_offset, flow, packed, bias, mask_scale, gt, valid, N,
+                             h, w, H, W, max_flow, workspace, workspace_bytes);
+    if (rc || (rc = check_ptr8(fn, out, "out"))) return rc;
+    return hip_status(launch_mask_upsample_loss(hidden, hidden_channels, hidden_offset, flow, packed, bias, mask_scale,
+                                                gt, valid, N, h, w, H, W, max_flow, want_metrics != 0, out, workspace,
+                                                (hipStream_t)stream),
+                      fn);
+}
+
+int corr_mask_upsample_loss_bwd(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                                const void *packed, const float *bias, float mask_scale, const float *gt,
+                                const float *valid, const float *scale, int N, int h, int w, int H, int W,
+                                float max_flow, float *dflow, float *dz, void *workspace, size_t workspace_bytes,
+                                void *stream) {
+    static const char *fn = "corr_mask_upsample_loss_bwd";
+    g_err[0] = 0;
+    int rc = check_mask_loss(fn, hidden, hidden_channels, hidden_offset, flow, packed, bias, mask_scale, gt, valid, N,
+                             h, w, H, W, max_flow, workspace, workspace_bytes);
+    if (rc || (rc = check_ptr(fn, scale, "scale")) || (rc = check_ptr(fn, dflow, "dflow")) ||
+        (rc = check_ptr(fn, dz, "dz")))
+        return rc;
+    return hip_status(launch_mask_upsample_loss_bwd(hidden, hidden_channels, hidden_offset, flow, packed, bias,
+                                                    mask_scale, gt, valid, scale, N, h, w, H, W, max_flow, dflow, dz,
+                                                    workspace, (hipStream_t)stream),
                       fn);
 }
 

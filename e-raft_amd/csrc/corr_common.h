@@ -180,6 +180,20 @@ hipError_t launch_sequence_loss(const float *pred, const float *gt, const float 
                                 float max_flow, bool metrics, double *out, void *ws, hipStream_t s);
 hipError_t launch_sequence_loss_bwd(const float *pred, const float *gt, const float *valid, const float *scale, int N,
                                     int H, int W, float max_flow, float *dpred, hipStream_t s);
+hipError_t launch_loss_finalize(const void *part, size_t nparts, double *out, hipStream_t s);
+// corr_mask_loss.hip: the same loss over the prediction of the mask head's logits, which both
+// directions recompute from `hidden` (launch_mask_upsample's inputs and pack); dz is the gradient
+// of the head's convolution output [N][576][h][w].
+size_t mask_upsample_loss_workspace(int N, int h, int w);
+hipError_t launch_mask_upsample_loss(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                                     const void *packed, const float *bias, float mask_scale, const float *gt,
+                                     const float *valid, int N, int h, int w, int H, int W, float max_flow,
+                                     bool metrics, double *out, void *ws, hipStream_t s);
+hipError_t launch_mask_upsample_loss_bwd(const float *hidden, int hidden_channels, int hidden_offset,
+                                         const float *flow, const void *packed, const float *bias, float mask_scale,
+                                         const float *gt, const float *valid, const float *scale, int N, int h,
+                                         int w, int H, int W, float max_flow, float *dflow, float *dz, void *ws,
+                                         hipStream_t s);
 size_t lookup_conv_weights_bytes();
 hipError_t launch_lookup_conv_weights(const float *w, int O, int C, void *packed, hipStream_t s);
 hipError_t launch_lookup_conv(const ConstLevelPtrs &pyr, const float *coords, int B, int NQ, int H, int W,

@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "corr_common.h"
+#include "corr_loss_math.h"
 #include "corr_upsample_math.h"
 
 namespace corr {
@@ -33,72 +34,6 @@ constexpr int kLossWaves = 8;
 constexpr int kLossThreads = 64 * kLossWaves;
 constexpr int kSeqPerThread = 8;                             // pixels of a thread: 16 L1 terms
 constexpr int kSeqPerBlock = kLossThreads * kSeqPerThread;  // pixels of a workgroup
-
-struct LossPartial {
-    double l1, epe;
-    unsigned long long n, c1, c3, c5;
-};
-static_assert(sizeof(LossPartial) == 48, "workspace layout");
-
-struct LossAcc {
-    float l1 = 0.0f, epe = 0.0f;
-    unsigned n = 0, c1 = 0, c3 = 0, c5 = 0;
-};
-
-__device__ inline float loss_valid(float vld, float gx, float gy, float max_flow) {
-    return (vld >= 0.5f && sqrtf(gx * gx + gy * gy) < max_flow) ? 1.0f : 0.0f;
-}
-
-__device__ inline float loss_sign(float d) { return (float)(d > 0.0f) - (float)(d < 0.0f); }
-
-template <bool METRICS>
-__device__ inline void loss_term(LossAcc &acc, float a0, float a1, float g0, float g1, float vld, float max_flow) {
-    const float v = loss_valid(vld, g0, g1, max_flow);
-    const float d0 = a0 - g0, d1 = a1 - g1;
-    acc.l1 += v * fabsf(d0);
-    acc.l1 += v * fabsf(d1);
-    if (v != 0.0f) {
-        acc.n += 1;
-        if (METRICS) {
-            const float epe = sqrtf(d0 * d0 + d1 * d1);
-            acc.epe += epe;
-            acc.c1 += epe < 1.0f;
-            acc.c3 += epe < 3.0f;
-            acc.c5 += epe < 5.0f;
-        }
-    }
-}
-
-// Every thread of the workgroup calls this (no early exit before it).
-__device__ inline void loss_block_reduce(const LossAcc &acc, LossPartial *dst) {
-    __shared__ double rd[kLossWaves][2];
-    __shared__ unsigned ri[kLossWaves][4];
-    double l1 = acc.l1, epe = acc.epe;
-    unsigned n = acc.n, c1 = acc.c1, c3 = acc.c3, c5 = acc.c5;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        l1 += __shfl_xor(l1, o);
-        epe += __shfl_xor(epe, o);
-        n += __shfl_xor(n, o);
-        c1 += __shfl_xor(c1, o);
-        c3 += __shfl_xor(c3, o);
-        c5 += __shfl_xor(c5, o);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) {
-        rd[wv][0] = l1, rd[wv][1] = epe;
-        ri[wv][0] = n, ri[wv][1] = c1, ri[wv][2] = c3, ri[wv][3] = c5;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        LossPartial p = {0.0, 0.0, 0, 0, 0, 0};
-        for (int v = 0; v < kLossWaves; ++v) {
-            p.l1 += rd[v][0], p.epe += rd[v][1];
-            p.n += ri[v][0], p.c1 += ri[v][1], p.c3 += ri[v][2], p.c5 += ri[v][3];
-        }
-        *dst = p;
-    }
-}
 
 template <bool METRICS>
 __global__ __launch_bounds__(kLossThreads) void upsample_loss_kernel(const float *__restrict__ flow,
@@ -132,7 +67,7 @@ __global__ __launch_bounds__(kLossThreads) void upsample_loss_kernel(const float
             loss_term<METRICS>(acc, a0, a1, g0p[X], g0p[HW + X], vp[X], max_flow);
         }
     }
-    loss_block_reduce(acc, part + blockIdx.x);
+    loss_block_reduce<kLossWaves>(acc, part + blockIdx.x);
 }
 
 template <bool METRICS>
@@ -151,7 +86,7 @@ __global__ __launch_bounds__(kLossThreads) void sequence_loss_kernel(const float
             loss_term<METRICS>(acc, pred[o], pred[o + HW], gt[o], gt[o + HW], valid[px], max_flow);
         }
     }
-    loss_block_reduce(acc, part + blockIdx.x);
+    loss_block_reduce<kLossWaves>(acc, part + blockIdx.x);
 }
 
 // One wave: lane L sums the partials of its contiguous index range in index order, lane 0 then
@@ -275,6 +210,11 @@ hipError_t finalize(const LossPartial *part, size_t nparts, double *out, hipStre
 }
 
 }  // namespace
+
+// The grid sum alone, for a caller that has written the LossPartial words itself (corr_mask_loss.hip).
+hipError_t launch_loss_finalize(const void *part, size_t nparts, double *out, hipStream_t s) {
+    return finalize(static_cast<const LossPartial *>(part), nparts, out, s);
+}
 
 // The 18 S planes of the backward; the forward's per-workgroup partials (48 bytes for at most 64
 // coarse pixels) fit in the same bytes.

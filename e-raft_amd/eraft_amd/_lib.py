@@ -47,6 +47,8 @@ TRAIN_EXPORTS = ("corr_upsample_loss_workspace", "corr_upsample_loss", "corr_ups
                  "corr_sequence_loss_workspace", "corr_sequence_loss", "corr_sequence_loss_bwd")
 # include/corr_mi355x_enc_prec.h: the encoders' convolutions in a precision mode
 ENC_PREC_EXPORTS = ("corr_enc_conv_forward_prec", "corr_enc_stem_forward_prec", "corr_enc_pw_forward_prec")
+# include/corr_mi355x_train_head.h: the fused loss with the mask head inside the launch
+TRAIN_HEAD_EXPORTS = ("corr_mask_upsample_loss_workspace", "corr_mask_upsample_loss", "corr_mask_upsample_loss_bwd")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
 
 # Build algorithms (include/corr_mi355x.h).  BF16X6 is the default: every fp32 feature split
@@ -197,7 +199,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_sequence_loss_workspace.argtypes, lib.corr_sequence_loss_workspace.restype = [i, i, i], sz
     lib.corr_sequence_loss.argtypes = [vp, vp, vp, i, i, i, fl, i, vp, vp, sz, vp]
     lib.corr_sequence_loss_bwd.argtypes = [vp, vp, vp, vp, i, i, i, fl, vp, vp]
+    lib.corr_mask_upsample_loss_workspace.argtypes, lib.corr_mask_upsample_loss_workspace.restype = [i, i, i], sz
+    lib.corr_mask_upsample_loss.argtypes = [vp, i, i, vp, vp, vp, fl, vp, vp, i, i, i, i, i, fl, i, vp, vp, sz, vp]
+    lib.corr_mask_upsample_loss_bwd.argtypes = [vp, i, i, vp, vp, vp, fl, vp, vp, vp, i, i, i, i, i, fl, vp, vp, vp,
+                                                sz, vp]
     for f in ("corr_upsample_loss", "corr_upsample_loss_bwd", "corr_sequence_loss", "corr_sequence_loss_bwd",
+              "corr_mask_upsample_loss", "corr_mask_upsample_loss_bwd",
               "corr_gru_half_step_prec", "corr_conv_forward_prec", *ENC_PREC_EXPORTS):
         getattr(lib, f).restype = i
     for f in ("corr_ondemand_lookup_conv", "corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
@@ -961,6 +968,58 @@ def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=
         _check(lib.corr_mask_upsample_forward(hp, hc, hidden_offset, fp, pk, bp, float(scale), B, H, W, op,
                                               _stream(hidden)))
     return out
+
+
+def _mask_loss_args(name, hidden, hidden_offset, flow, packed, bias, gt, valid):
+    """The sizes and pointers that corr_mask_upsample_loss and its backward share."""
+    if not isinstance(hidden, torch.Tensor) or hidden.dim() != 4:
+        raise ValueError(f"{name}: hidden must be a tensor [N, C, h, w]")
+    N, hc, h, w = hidden.shape
+    hidden_offset = int(hidden_offset)
+    hp = _window_arg(hidden, "hidden", N, h, w, hidden_offset, 256, hidden.device)
+    fp = _dev(flow, "flow")
+    if tuple(flow.shape) != (N, 2, h, w) or flow.device != hidden.device:
+        raise ValueError(f"{name}: flow must be [{N}, 2, {h}, {w}] on {hidden.device} (got {tuple(flow.shape)} on "
+                         f"{flow.device})")
+    H, W = _loss_frame(name, gt, valid, N)
+    if not (0 < H <= 8 * h and 0 < W <= 8 * w):
+        raise ValueError(f"{name}: a {H}x{W} loss frame does not lie in the {8 * h}x{8 * w} prediction")
+    lib = load()
+    pk = _pack_arg(packed, lib.corr_mask_upsample_weights_bytes(), hidden.device, "the mask head")
+    bp = _bias_arg(bias, 576, hidden.device, optional=False)
+    ws = torch.empty((lib.corr_mask_upsample_loss_workspace(N, h, w) + 7) // 8, dtype=torch.float64,
+                     device=hidden.device)
+    return lib, (hp, hc, hidden_offset, fp, pk, bp), (_dev(gt, "gt"), _dev(valid, "valid")), (N, h, w, H, W), ws
+
+
+def mask_upsample_loss(hidden, hidden_offset, flow, packed, bias, scale, gt, valid, max_flow, want_metrics):
+    """corr_mask_upsample_loss: the six fp64 words (include/corr_mi355x_train.h) of the prediction
+    that mask_upsample_forward would store for the same inputs, cropped to gt's H x W."""
+    lib, head, frame, dims, ws = _mask_loss_args("mask_upsample_loss", hidden, hidden_offset, flow, packed, bias, gt,
+                                                 valid)
+    out = torch.empty(6, dtype=torch.float64, device=hidden.device)
+    with torch.cuda.device(hidden.device):
+        _check(lib.corr_mask_upsample_loss(*head, float(scale), *frame, *dims, float(max_flow),
+                                           int(bool(want_metrics)), out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                           _stream(hidden)))
+    return out
+
+
+def mask_upsample_loss_bwd(hidden, hidden_offset, flow, packed, bias, scale, gt, valid, grad_scale, max_flow):
+    """corr_mask_upsample_loss_bwd: grad_scale is a one-element fp32 device tensor -> (dflow, dz),
+    dz [N, 576, h, w] the gradient of the head's convolution output."""
+    lib, head, frame, dims, ws = _mask_loss_args("mask_upsample_loss_bwd", hidden, hidden_offset, flow, packed, bias,
+                                                 gt, valid)
+    if grad_scale.numel() != 1:
+        raise ValueError(f"mask_upsample_loss_bwd: scale must hold one float (got {tuple(grad_scale.shape)})")
+    N, h, w = dims[:3]
+    dflow = torch.empty_like(flow)
+    dz = torch.empty((N, 576, h, w), dtype=torch.float32, device=hidden.device)
+    with torch.cuda.device(hidden.device):
+        _check(lib.corr_mask_upsample_loss_bwd(*head, float(scale), *frame, _dev(grad_scale, "scale"), *dims,
+                                               float(max_flow), _dev(dflow, "dflow"), _dev(dz, "dz"), ws.data_ptr(),
+                                               ws.numel() * 8, _stream(hidden)))
+    return dflow, dz
 
 
 def flow_enc_pack_weights(w):

@@ -20,11 +20,11 @@ SOURCES = ["corr_build.hip", "corr_build_split.hip", "corr_build_bf16.hip", "cor
            "corr_bwd.hip",
            "corr_bwd_split.hip", "corr_splat.hip", "corr_upsample.hip", "corr_voxel.hip", "corr_gru.hip",
            "corr_conv.hip", "corr_enc_front.hip", "corr_mask_upsample.hip", "corr_flow.hip", "corr_loss.hip",
-           "corr_api.cpp"]
+           "corr_mask_loss.hip", "corr_api.cpp"]
 # every header counts as a dependency of every translation unit (paths relative to csrc/)
 HEADERS = sorted(glob.glob("*.h", root_dir=SRC)) + [os.path.join("..", "..", "include", h)
                                                     for h in ("corr_mi355x.h", "corr_mi355x_enc_prec.h",
-                                                              "corr_mi355x_train.h")]
+                                                              "corr_mi355x_train.h", "corr_mi355x_train_head.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the lookup / pool arithmetic is specified op-by-op (each fp32 op rounds

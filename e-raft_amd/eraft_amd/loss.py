@@ -9,7 +9,12 @@ On the MI355X it runs on the kernels of csrc/corr_loss.hip, in two forms:
                                        is one fused launch pair forward (corr_upsample_loss) and
                                        one backward (corr_upsample_loss_bwd), so neither the
                                        full-resolution prediction nor its gradient is ever stored
-                                       (ERAFT.forward(..., sequence_loss=crit)).
+                                       (ERAFT.forward(..., sequence_loss=crit)); add_hidden takes
+                                       relu(mask[0](net)) and the head mask[2] instead of the mask
+                                       and runs the head inside the launches (csrc/corr_mask_loss.hip:
+                                       corr_mask_upsample_loss forward, corr_mask_upsample_loss_bwd
+                                       and the convolution's backward over dz), so no mask is stored
+                                       or saved either (ERAFT.fuse_mask_loss).
 Anything that is not an fp32 GPU tensor goes through the plain torch composition below.  Nothing
 here synchronises: the metrics are 0-dim tensors, float(m["epe"]) is the reference's .item().
 """
@@ -110,6 +115,47 @@ class _UpsampleLossFn(torch.autograd.Function):
         return dflow, dmask, None, None, None, None, None
 
 
+class _MaskHeadLossFn(torch.autograd.Function):
+    """One term of the prediction upsample_flow(flow, scale * conv(hidden))[..., pad_h:, pad_w:] for
+    the 1x1 mask head `conv`: saves hidden, flow and the parameters, never a mask; its backward
+    recomputes the logits, and the head's own gradients are aten's convolution_backward over dz."""
+
+    @staticmethod
+    def forward(ctx, hidden, flow, weight, bias, gt, valid, conv, mask_scale, max_flow, coef, want_metrics):
+        from . import _lib
+        from .upsample import _mask_pack, channel_window
+        packed, pbias = _mask_pack(conv)
+        buf, off = channel_window(hidden)
+        stats = _lib.mask_upsample_loss(buf, off, flow, packed, pbias, mask_scale, gt, valid, max_flow, want_metrics)
+        ctx.save_for_backward(hidden, flow, weight, bias, gt, valid)
+        ctx.conv, ctx.mask_scale, ctx.max_flow, ctx.coef = conv, mask_scale, max_flow, coef
+        ctx.mark_non_differentiable(stats)
+        return (stats[0] * coef).float(), stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad, _grad_stats):
+        from . import _lib
+        from .upsample import _mask_pack, channel_window
+        hidden, flow, weight, bias, gt, valid = ctx.saved_tensors
+        packed, pbias = _mask_pack(ctx.conv)
+        buf, off = channel_window(hidden)
+        dflow, dz = _lib.mask_upsample_loss_bwd(buf, off, flow, packed, pbias, ctx.mask_scale, gt, valid,
+                                                _scale(grad, ctx.coef), ctx.max_flow)
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+        dhidden = dweight = dbias = None
+        if any(need):
+            dhidden, dweight, dbias = torch.ops.aten.convolution_backward(
+                dz, hidden, weight, [576], [1, 1], [0, 0], [1, 1], False, [0, 0], 1, list(need))
+        return dhidden, dflow, dweight, dbias, None, None, None, None, None, None, None
+
+
+def _is_mask_head(conv):
+    return (isinstance(conv, torch.nn.Conv2d) and tuple(conv.weight.shape) == (576, 256, 1, 1)
+            and conv.bias is not None and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.weight.is_cuda and conv.weight.dtype == conv.bias.dtype == torch.float32)
+
+
 class SequenceLoss:
     """The sequence loss as a criterion that takes its predictions one at a time.
 
@@ -170,6 +216,27 @@ class SequenceLoss:
             self._record(index, total, term, lambda: _metrics(stats))
         else:
             self.add(_torch_upsample(flow, mask)[..., ph:, pw:], index, total)
+
+    def add_hidden(self, conv, hidden, flow, index, total, pad=(0, 0), scale=0.25):
+        """The same term as add_upsampled(flow, scale * conv(hidden), ...) from hidden =
+        relu(mask[0](net)) [B, 256, h, w] (a channel slice of a wider contiguous buffer is read in
+        place) and the mask head `conv`.  With fp32 GPU tensors and a 256 -> 576 1x1 `conv` with a
+        bias the head runs inside the fused launches and no mask is stored or saved for backward."""
+        ph, pw = int(pad[0]), int(pad[1])
+        H, W = self.flow_gt.shape[2:]
+        if (flow.dim() != 4 or hidden.dim() != 4 or (8 * flow.shape[2] - ph, 8 * flow.shape[3] - pw) != (H, W)
+                or ph < 0 or pw < 0 or hidden.shape[0] != flow.shape[0] or hidden.shape[2:] != flow.shape[2:]):
+            raise ValueError(f"SequenceLoss: hidden {tuple(hidden.shape)}, flow {tuple(flow.shape)} with pad "
+                             f"{(ph, pw)} do not upsample to flow_gt's {H}x{W}")
+        if (self.hip and _on_hip(hidden, flow) and _is_mask_head(conv) and hidden.shape[1] == 256
+                and hidden.device == flow.device == conv.weight.device == self.flow_gt.device):
+            term, stats = _MaskHeadLossFn.apply(hidden, flow.contiguous(), conv.weight, conv.bias, self.flow_gt,
+                                                self.valid, conv, float(scale), self.max_flow,
+                                                self._weight(index, total) / self.flow_gt.numel(),
+                                                index == total - 1)
+            self._record(index, total, term, lambda: _metrics(stats))
+        else:
+            self.add_upsampled(flow, scale * conv(hidden), index, total, pad)
 
     def result(self):
         """(loss, metrics) of the predictions added so far; metrics is None until the last one is."""

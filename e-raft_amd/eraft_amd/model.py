@@ -359,6 +359,11 @@ class ERAFT(nn.Module):
     # HBM, no torch convc1); under autograd it is the unfused composition.  Default off (DESIGN §21
     # has the measurements).
     fuse_ondemand_conv = os.environ.get("ERAFT_AMD_ONDEMAND_FUSE_CONV", "0") == "1"
+    # ERAFT_AMD_FUSE_MASK_LOSS=1: with a sequence_loss criterion the mask head's 1x1 convolution and
+    # its 0.25 run inside the fused upsampling loss (SequenceLoss.add_hidden: corr_mask_upsample_loss
+    # forward, corr_mask_upsample_loss_bwd + the convolution's backward over dz), so the 576-channel
+    # mask is neither stored nor saved for backward.  Default off (DESIGN §32 has the measurements).
+    fuse_mask_loss = os.environ.get("ERAFT_AMD_FUSE_MASK_LOSS", "0") == "1"
     # The precision mode of the GRU and the update block's 3x3 convolutions ("bf16x6", "bf16x3" or
     # "bf16": precision.py), and that of the two encoders' convolutions; an instance takes each from
     # its config (below).
@@ -436,7 +441,8 @@ class ERAFT(nn.Module):
         flow and the mask (add_upsampled: on the MI355X the loss fused with the upsampling, no
         full-resolution prediction stored; the torch composition elsewhere) instead of calling
         upsample_flow; the returned list of predictions is empty and the caller reads
-        sequence_loss.result().  Works under no_grad for validation."""
+        sequence_loss.result().  Works under no_grad for validation.  With `fuse_mask_loss` the
+        criterion gets relu(mask[0](net)) and the head mask[2] instead of the mask (add_hidden)."""
         image1 = self.image_padder.pad(image1).contiguous()
         image2 = self.image_padder.pad(image2).contiguous()
         fmap1, fmap2 = self.fnet([image1, image2])
@@ -478,12 +484,19 @@ class ERAFT(nn.Module):
                     from .update import UpdateWorkspace
                     ws = UpdateWorkspace(inp.detach())
                 kw = {"workspace": ws, "coords1": coords1, "coords0": coords0}
+            pad = (self.image_padder.pad_height, self.image_padder.pad_width)
+            if sequence_loss is not None and self.fuse_mask_loss:
+                # the criterion runs the mask head itself (add_hidden takes the torch composition
+                # for tensors its kernels are not built for)
+                net, hidden, delta, *upd = ub(net, inp, corr, flow, fuse, defer_mask=True, **kw)
+                coords1, flow = upd if tail else (coords1 + delta, None)
+                sequence_loss.add_hidden(ub.mask[2], hidden, flow if tail else coords1 - coords0, it, iters, pad)
+                continue
             if sequence_loss is not None:
                 # the criterion needs the mask itself: the inference-only mask head fusion is not taken
                 net, up_mask, delta, *upd = ub(net, inp, corr, flow, fuse, **kw)
                 coords1, flow = upd if tail else (coords1 + delta, None)
-                sequence_loss.add_upsampled(flow if tail else coords1 - coords0, up_mask, it, iters,
-                                            (self.image_padder.pad_height, self.image_padder.pad_width))
+                sequence_loss.add_upsampled(flow if tail else coords1 - coords0, up_mask, it, iters, pad)
                 continue
             if self.fuse_mask_upsample and self._mask_fusable(net, inp, corr, coords1):
                 from .upsample import channel_window, mask_upsample

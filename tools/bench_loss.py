@@ -9,7 +9,15 @@ spread drops out; a step's time is wall time per step over a window that ends wi
 synchronisation (the host's enqueueing of the chain's launches is part of what a trainer pays).
     python tools/bench_loss.py [--sizes dsec,b8,hires1920] [--trials 5] [--steps N] [--json profiles/loss_bench.json]
 Per size: median / min / max ms per step over the windows, torch.cuda.max_memory_allocated of a
-step above the inputs' own bytes, and the two losses.  Prints one JSON document."""
+step above the inputs' own bytes, and the two losses.  Prints one JSON document.
+
+--mask-head measures the tail with the mask head in it instead: forward and backward to every
+(hidden_i, flow_i) and to the head's parameters, alternated in the same way.
+    mask    today's path: torch mask[2] (MIOpen 1x1, 256 -> 576), 0.25 *, add_upsampled: a mask per
+            iteration is stored and saved for backward
+    hidden  SequenceLoss.add_hidden (corr_mask_upsample_loss; corr_mask_upsample_loss_bwd + the
+            convolution's backward over dz): no mask is stored or saved
+    python tools/bench_loss.py --mask-head --json profiles/loss_mask_head_bench.json"""
 import argparse
 import json
 import os
@@ -50,29 +58,61 @@ def chain_step(flows, masks, gt, valid):
     return loss.detach()
 
 
+def mask_step(hiddens, flows, gt, valid, conv):
+    crit = SequenceLoss(gt, valid, GAMMA, MAX_FLOW)
+    for i, (x, f) in enumerate(zip(hiddens, flows)):
+        crit.add_upsampled(f, 0.25 * conv(x), i, ITERS)
+    loss, _ = crit.result()
+    loss.backward()
+    return loss.detach()
+
+
+def hidden_step(hiddens, flows, gt, valid, conv):
+    crit = SequenceLoss(gt, valid, GAMMA, MAX_FLOW)
+    for i, (x, f) in enumerate(zip(hiddens, flows)):
+        crit.add_hidden(conv, x, f, i, ITERS)
+    loss, _ = crit.result()
+    loss.backward()
+    return loss.detach()
+
+
 def run(step, args):
     for t in args[0] + args[1]:
         t.grad = None
+    if len(args) > 4:
+        args[4].zero_grad(set_to_none=True)
     return step(*args)
 
 
-def bench_size(name, trials, dev, steps=None):
+def bench_size(name, trials, dev, steps=None, mask_head=False):
     B, h, w = SIZES[name]
     gen = torch.Generator(device=dev).manual_seed(1234)
     flows = [(2.0 * torch.randn(B, 2, h, w, device=dev, generator=gen)).requires_grad_(True) for _ in range(ITERS)]
-    masks = [(2.0 * torch.randn(B, 576, h, w, device=dev, generator=gen)).requires_grad_(True) for _ in range(ITERS)]
     gt = 4.0 * torch.randn(B, 2, 8 * h, 8 * w, device=dev, generator=gen)
     valid = (torch.rand(B, 8 * h, 8 * w, device=dev, generator=gen) < 0.9).float()
-    args = (flows, masks, gt, valid)
+    if mask_head:
+        # relu(gauss) activations and a head whose mask has sigma 2, as the other mode's masks
+        hiddens = [torch.relu(torch.randn(B, 256, h, w, device=dev, generator=gen)).requires_grad_(True)
+                   for _ in range(ITERS)]
+        conv = torch.nn.Conv2d(256, 576, 1).to(dev)
+        with torch.no_grad():
+            conv.weight.copy_(8.0 / 128 ** 0.5 * torch.randn(576, 256, 1, 1, device=dev, generator=gen))
+        args = (hiddens, flows, gt, valid, conv)
+        variants, (old, new) = {"mask": mask_step, "hidden": hidden_step}, ("mask", "hidden")
+    else:
+        masks = [(2.0 * torch.randn(B, 576, h, w, device=dev, generator=gen)).requires_grad_(True) for _ in range(ITERS)]
+        args = (flows, masks, gt, valid)
+        variants, (old, new) = {"chain": chain_step, "fused": fused_step}, ("chain", "fused")
     steps = steps or max(5, int(200 / max(1.0, B * h * w / 4800.0)))  # windows of about half a second
-    variants = {"chain": chain_step, "fused": fused_step}
     res = {"B": B, "h": h, "w": w, "H": 8 * h, "W": 8 * w, "iters": ITERS, "steps_per_window": steps, "windows": trials}
     times = {n: [] for n in variants}
     for n, step in variants.items():  # warm up, then the peak memory of one step above what is live before it
         for _ in range(2):
             loss = run(step, args)
-        for t in flows + masks:
+        for t in args[0] + args[1]:
             t.grad = None
+        if mask_head:
+            conv.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()
@@ -92,9 +132,10 @@ def bench_size(name, trials, dev, steps=None):
         v = sorted(v)
         res[n].update({"step_ms_median": round(v[len(v) // 2], 4), "step_ms_min": round(v[0], 4),
                        "step_ms_max": round(v[-1], 4)})
-    res["fused_over_chain_time"] = round(res["fused"]["step_ms_median"] / res["chain"]["step_ms_median"], 3)
-    res["fused_over_chain_peak"] = round(res["fused"]["peak_bytes_above_inputs"] / res["chain"]["peak_bytes_above_inputs"], 3)
-    del flows, masks, args
+    res[f"{new}_over_{old}_time"] = round(res[new]["step_ms_median"] / res[old]["step_ms_median"], 3)
+    res[f"{new}_over_{old}_peak"] = round(res[new]["peak_bytes_above_inputs"] / res[old]["peak_bytes_above_inputs"], 3)
+    del flows, args
+    hiddens = masks = conv = None  # noqa: F841  (before empty_cache)
     torch.cuda.empty_cache()
     return res
 
@@ -105,17 +146,23 @@ def main():
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--json", default=None)
     ap.add_argument("--steps", type=int, default=None, help="steps per window (default: by size; small under a profiler)")
+    ap.add_argument("--mask-head", action="store_true", help="the tail with the mask head in it: mask[2] + add_upsampled "
+                    "against add_hidden")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_loss needs an MI355X (the fused path has no CPU kernels)")
     if a.trials < 5:
         sys.exit("--trials must be >= 5 (the median of at least 5 windows is reported)")
     dev = torch.device("cuda", 0)
-    doc = {"device": torch.cuda.get_device_name(0),
-           "call": "12 iterations' sequence loss, forward + backward to every (flow_i, mask_i), eager, variants "
-                   "alternated; chain: corr_convex_upsample + torch loss + corr_convex_upsample_bwd; fused: "
-                   "corr_upsample_loss + corr_upsample_loss_bwd",
-           "sizes": {n: bench_size(n, a.trials, dev, a.steps) for n in a.sizes.split(",")}}
+    call = ("12 iterations' sequence loss, forward + backward to every (flow_i, mask_i), eager, variants "
+            "alternated; chain: corr_convex_upsample + torch loss + corr_convex_upsample_bwd; fused: "
+            "corr_upsample_loss + corr_upsample_loss_bwd")
+    if a.mask_head:
+        call = ("12 iterations' mask head + sequence loss, forward + backward to every (hidden_i, flow_i) and to the "
+                "head's parameters, eager, variants alternated; mask: torch mask[2], 0.25 *, corr_upsample_loss / _bwd; "
+                "hidden: corr_mask_upsample_loss, corr_mask_upsample_loss_bwd + aten convolution_backward over dz")
+    doc = {"device": torch.cuda.get_device_name(0), "call": call,
+           "sizes": {n: bench_size(n, a.trials, dev, a.steps, a.mask_head) for n in a.sizes.split(",")}}
     text = json.dumps(doc, indent=1)
     print(text)
     if a.json:
