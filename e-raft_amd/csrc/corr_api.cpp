@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "../../include/corr_mi355x_build_prec.h"
 #include "../../include/corr_mi355x_enc_prec.h"
 #include "../../include/corr_mi355x_train.h"
 #include "../../include/corr_mi355x_train_head.h"
@@ -158,20 +159,31 @@ size_t corr_build_workspace(int algo, int B, int D, int NQ, int H, int W) {
     return (size_t)-1;
 }
 
-int corr_build_ex(int algo, const float *fmap1_rows, int NQ, const float *fmap2, int B, int D,
-                  int H, int W, int levels, float *const *pyr, void *workspace,
-                  size_t workspace_bytes, void *stream) {
-    static const char *fn = "corr_build_ex";
-    if (algo == CORR_BUILD_FP32) return corr_build_rows(fmap1_rows, NQ, fmap2, B, D, H, W, levels, pyr, stream);
+// CORR_PREC_* of the build (corr_mi355x_build_prec.h): an unknown mode is refused before every
+// other check, a reduced one runs on CORR_BUILD_BF16X6 only (phase flags allowed).
+static int check_build_precision(const char *fn, int algo, int precision) {
+    if (!precision_supported(precision))
+        return fail(CORR_EINVAL, "%s: precision must be CORR_PREC_BF16X6 (0), _BF16X3 (1) or _BF16 (2) (got %d)", fn,
+                    precision);
+    if (precision != CORR_PREC_BF16X6 && (algo & ~(CORR_BUILD_ONLY_PACK | CORR_BUILD_ONLY_MFMA)) != CORR_BUILD_BF16X6)
+        return fail(CORR_EUNSUPPORTED, "%s: a reduced precision needs CORR_BUILD_BF16X6 (got algorithm %d)", fn, algo);
+    return CORR_OK;
+}
+
+static int build_ex(const char *fn, int algo, const float *fmap1_rows, int NQ, const float *fmap2, int B, int D, int H,
+                    int W, int levels, float *const *pyr, void *workspace, size_t workspace_bytes, void *stream,
+                    int precision) {
     g_err[0] = 0;
+    int rc = check_build_precision(fn, algo, precision);
+    if (rc) return rc;
+    if (algo == CORR_BUILD_FP32) return corr_build_rows(fmap1_rows, NQ, fmap2, B, D, H, W, levels, pyr, stream);
     const int phase = algo & (CORR_BUILD_ONLY_PACK | CORR_BUILD_ONLY_MFMA);
     algo &= ~(CORR_BUILD_ONLY_PACK | CORR_BUILD_ONLY_MFMA);
     if ((algo != CORR_BUILD_F16X3 && algo != CORR_BUILD_BF16X6) ||
         phase == (CORR_BUILD_ONLY_PACK | CORR_BUILD_ONLY_MFMA))
         return fail(CORR_EINVAL, "%s: unknown algorithm %d", fn, algo | phase);
     const bool bf = algo == CORR_BUILD_BF16X6;
-    int rc = check_dims(fn, B, NQ, H, W, levels);
-    if (rc) return rc;
+    if ((rc = check_dims(fn, B, NQ, H, W, levels))) return rc;
     if (D < 1) return fail(CORR_EINVAL, "%s: D must be >= 1 (got %d)", fn, D);
     if (!bf && !build_split_supported(D))
         return fail(CORR_EUNSUPPORTED, "%s: D = %d is too large for CORR_BUILD_F16X3", fn, D);
@@ -185,16 +197,33 @@ int corr_build_ex(int algo, const float *fmap1_rows, int NQ, const float *fmap2,
     const int part = phase == CORR_BUILD_ONLY_PACK ? 1 : phase == CORR_BUILD_ONLY_MFMA ? 2 : 0;
     if (bf)
         return hip_status(
-            launch_build_bf16(fmap1_rows, NQ, fmap2, B, D, H, W, levels, lp, workspace, (hipStream_t)stream, part), fn);
+            launch_build_bf16(fmap1_rows, NQ, fmap2, B, D, H, W, levels, lp, workspace, (hipStream_t)stream, part, precision),
+            fn);
     return hip_status(launch_build_split(fmap1_rows, NQ, fmap2, B, D, H, W, levels, lp, workspace, (hipStream_t)stream, part),
                       fn);
 }
 
-int corr_build_region(int algo, const float *fmap1_rows, int NQ, const float *fmap2_rows, int y0, int y1, int B,
-                      int D, int H, int W, int levels, float *const *pyr, void *workspace, size_t workspace_bytes,
-                      int flags, void *stream) {
-    static const char *fn = "corr_build_region";
+int corr_build_ex(int algo, const float *fmap1_rows, int NQ, const float *fmap2, int B, int D,
+                  int H, int W, int levels, float *const *pyr, void *workspace,
+                  size_t workspace_bytes, void *stream) {
+    return build_ex("corr_build_ex", algo, fmap1_rows, NQ, fmap2, B, D, H, W, levels, pyr, workspace, workspace_bytes,
+                    stream, CORR_PREC_BF16X6);
+}
+
+int corr_build_ex_prec(int algo, const float *fmap1_rows, int NQ, const float *fmap2, int B, int D, int H, int W,
+                       int levels, float *const *pyr, void *workspace, size_t workspace_bytes, int precision,
+                       void *stream) {
+    return build_ex("corr_build_ex_prec", algo, fmap1_rows, NQ, fmap2, B, D, H, W, levels, pyr, workspace,
+                    workspace_bytes, stream, precision);
+}
+
+static int build_region(const char *fn, int algo, const float *fmap1_rows, int NQ, const float *fmap2_rows, int y0,
+                        int y1, int B, int D, int H, int W, int levels, float *const *pyr, void *workspace,
+                        size_t workspace_bytes, int flags, void *stream, int precision) {
     g_err[0] = 0;
+    if (!precision_supported(precision))
+        return fail(CORR_EINVAL, "%s: precision must be CORR_PREC_BF16X6 (0), _BF16X3 (1) or _BF16 (2) (got %d)", fn,
+                    precision);
     if (algo != CORR_BUILD_BF16X6)
         return fail(CORR_EUNSUPPORTED, "%s: only CORR_BUILD_BF16X6 builds by target region (got %d)", fn, algo);
     int rc = check_dims(fn, B, NQ, H, W, levels);
@@ -212,8 +241,22 @@ int corr_build_region(int algo, const float *fmap1_rows, int NQ, const float *fm
     LevelPtrs lp{};
     if ((rc = check_pyramid(fn, pyr, levels, "pyr", lp.p))) return rc;
     return hip_status(launch_build_bf16_region(fmap1_rows, NQ, fmap2_rows, y0, y1, B, D, H, W, levels, lp, workspace,
-                                               (flags & CORR_REGION_PACK_QUERIES) != 0, (hipStream_t)stream),
+                                               (flags & CORR_REGION_PACK_QUERIES) != 0, (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_build_region(int algo, const float *fmap1_rows, int NQ, const float *fmap2_rows, int y0, int y1, int B,
+                      int D, int H, int W, int levels, float *const *pyr, void *workspace, size_t workspace_bytes,
+                      int flags, void *stream) {
+    return build_region("corr_build_region", algo, fmap1_rows, NQ, fmap2_rows, y0, y1, B, D, H, W, levels, pyr,
+                        workspace, workspace_bytes, flags, stream, CORR_PREC_BF16X6);
+}
+
+int corr_build_region_prec(int algo, const float *fmap1_rows, int NQ, const float *fmap2_rows, int y0, int y1, int B,
+                           int D, int H, int W, int levels, float *const *pyr, void *workspace,
+                           size_t workspace_bytes, int flags, int precision, void *stream) {
+    return build_region("corr_build_region_prec", algo, fmap1_rows, NQ, fmap2_rows, y0, y1, B, D, H, W, levels, pyr,
+                        workspace, workspace_bytes, flags, stream, precision);
 }
 
 int corr_build(const float *fmap1, const float *fmap2, int B, int D, int H, int W, int levels,

@@ -62,11 +62,14 @@ constexpr int kPatchRows = 8;                           // target patch: 8 rows 
 constexpr int kWaves = 4, kQPerWave = 32;               // 2 query blocks per wave
 constexpr int kQPerWG = kWaves * kQPerWave;             // 128
 constexpr int kRing = 3;                                // LDS ring slots (prefetch distance 2)
-constexpr int kSlotBytes = kPatchRows * kPieces * 1024; // 24 KiB per K step
-constexpr int kLds = kRing * kSlotBytes;                // 72 KiB
-constexpr int kDmaPerWave = kPatchRows * kPieces / kWaves;  // 6 LDS-DMA pieces per wave and step
-constexpr int kQLoads = 2 * kPieces;                    // query loads per wave and step
 constexpr int kPixBytes = kStepK * kPieces * 2;         // workspace bytes per pixel and K step
+// What follows the number of pieces a kernel keeps of both operands (NP = 3: hi, mid, lo, the
+// default; 2: hi, mid; 1: hi — CORR_PREC_*): a reduced kernel neither stages, loads nor
+// multiplies the dropped pieces.  The record stride in the workspace stays 3 KiB in every mode.
+constexpr int slot_bytes(int np) { return kPatchRows * np * 1024; }     // 24 / 16 / 8 KiB per K step
+constexpr int lds_bytes(int np) { return kRing * slot_bytes(np); }      // 72 / 48 / 24 KiB
+constexpr int dma_per_wave(int np) { return kPatchRows * np / kWaves; } // 6 / 4 / 2 LDS-DMA pieces per wave and step
+constexpr int q_loads(int np) { return 2 * np; }                        // 6 / 4 / 2 query loads per wave and step
 
 struct Geom {
     int S, NQp, NQB, NQG, Hp, CB, Wp;
@@ -125,12 +128,14 @@ struct PackArgs {
 // R: records per wave, all R records' loads issued before any split or store (more bytes in
 // flight per wave); the workgroup's 4 waves take 4 consecutive records at each r, so a k row is
 // still read as one 256-B run per workgroup.
-template <int R = 1>
+// NP: pieces stored (a reduced build never reads the others: their bytes keep whatever the
+// workspace held).
+template <int R = 1, int NP = kPieces>
 __global__ __launch_bounds__(256) void bf16_pack_kernel(PackArgs a) {
     const int z = blockIdx.z + a.z0, b = blockIdx.y;
     const int nblk = a.nblk[z];
     const int lane = threadIdx.x & 63, ci = lane & 15, grp = lane >> 4;
-    const int NP = a.np[z];
+    const int npix = a.np[z];
     float v[R][8];
     bool live[R];
     size_t dst[R];
@@ -156,9 +161,9 @@ __global__ __launch_bounds__(256) void bf16_pack_kernel(PackArgs a) {
         }
         valid = valid && live[r];
         const int k0 = s * kStepK + 8 * grp;
-        const float *src = a.f[z] + (size_t)b * a.D * NP + (valid ? n : 0);
+        const float *src = a.f[z] + (size_t)b * a.D * npix + (valid ? n : 0);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[r][j] = (valid && k0 + j < a.D) ? src[(size_t)(k0 + j) * NP] : 0.f;
+        for (int j = 0; j < 8; ++j) v[r][j] = (valid && k0 + j < a.D) ? src[(size_t)(k0 + j) * npix] : 0.f;
         dst[r] = (((size_t)b * a.S + s) * a.img[z] + iblk) * kRecU + lane;
     }
 #pragma unroll
@@ -170,8 +175,8 @@ __global__ __launch_bounds__(256) void bf16_pack_kernel(PackArgs a) {
         const u32x4_t h{hh[0], hh[1], hh[2], hh[3]}, m{mm[0], mm[1], mm[2], mm[3]}, l{ll[0], ll[1], ll[2], ll[3]};
         u32x4_t *out = a.pk[z] + dst[r];
         out[0] = h;
-        out[64] = m;
-        out[128] = l;
+        if constexpr (NP > 1) out[64] = m;
+        if constexpr (NP > 2) out[128] = l;
     }
 }
 
@@ -255,10 +260,22 @@ __device__ __forceinline__ Tile xcd_block_tile(const Args &p, int t) {
 // measured and dropped: bit-identical, 5-15 % slower at every size,
 // profiles/r06k_kbench_build_8waves_dropped.txt.)
 // FAST: levels == 4 (no level-count branches in the epilogue).
-template <int SS, int NR, bool ACC2, int VF = 0, bool FAST = false>
+// NP: pieces kept of both operands (CORR_PREC_*: 3 = bf16x6, the default; 2 = bf16x3; 1 = bf16),
+// and with them the products of a K step, smallest weight first (products<NP>() of
+// corr_bf16x6.h, mirrored on this kernel's fragments):
+//   NP = 3   the six above                                              acc, acs, split_sum
+//   NP = 2   acs += mid_t hi_q;  acs += hi_t mid_q;  acc += hi_t hi_q   acc, acs, split_sum
+//   NP = 1   acc += hi_t hi_q                                            acc alone
+// A reduced kernel stages 8 NP KiB per K step (2 NP LDS-DMA pieces per wave), loads 2 NP query
+// registers per step, reads NP fragments and issues 6 (NP = 2) or 2 (NP = 1) MFMAs per map row
+// where the default has 12; ring depth, workgroups per CU and the K order are the default's.
+// ACC2 only (the library's form).
+template <int SS, int NR, bool ACC2, int VF = 0, bool FAST = false, int NP = kPieces>
 __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
+    static_assert(NP == kPieces || ACC2, "the reduced modes exist in the two-accumulator form only");
     constexpr int QS = ACC2 ? 3 : 4, QD = QS - 1;
-    constexpr int WV = kWaves, QPWG = kQPerWG, DPW = kDmaPerWave;
+    constexpr int WV = kWaves, QPWG = kQPerWG, DPW = dma_per_wave(NP);
+    constexpr int kSlotBytes = slot_bytes(NP), kQLoads = q_loads(NP);
     extern __shared__ __attribute__((aligned(16))) char smem_bf16[];
     char *smem = smem_bf16;
 
@@ -272,15 +289,17 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
 
     // LDS-DMA pieces of this wave: pc = w + 4 m (m < 6) -> patch record rp = pc / 3 (tile row rp / 4,
     // tile column rp % 4 of the patch), piece pc % 3, landing at slot offset pc KiB (record rp's
-    // pieces at 3 rp .. 3 rp + 2).
+    // pieces at 3 rp .. 3 rp + 2).  NP pieces kept: pc = w + 4 m (m < 2 NP) -> record pc / NP, piece
+    // pc % NP of it (source: the record's 3-KiB stride, piece * 1 KiB), landing at slot offset
+    // pc KiB again, record rp's kept pieces at NP rp .. NP rp + NP - 1 — every pc < 8 NP once.
     const int TCp = 4 * p.CB;                          // tiles per row of the target image
     const size_t tstep = (size_t)p.Hp * p.CB * kRecU;  // u32x4 per K step of the target image
     const u32x4_t *tbase = p.pt + (((size_t)b * S * (p.Hp >> 2) + (y0 >> 2)) * TCp + 4 * tl.cb) * kRecU + lane;
     unsigned toff[DPW];
 #pragma unroll
     for (int m = 0; m < DPW; ++m) {
-        const int pc = w + WV * m, rp = pc / kPieces;
-        toff[m] = (unsigned)(((rp >> 2) * TCp + (rp & 3)) * kRecU + (pc % kPieces) * 64);
+        const int pc = w + WV * m, rp = pc / NP;
+        toff[m] = (unsigned)(((rp >> 2) * TCp + (rp & 3)) * kRecU + (pc % NP) * 64);
     }
     const size_t qstep = (size_t)p.NQB * kRecU;
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_void_t *)smem;
@@ -293,12 +312,24 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
     // older than T(k); the query registers then pass through an empty asm, before which the
     // compiler's own wait (it counts only the query loads: Q(k + 1), Q(k + 2) younger) is
     // already satisfied: no drain.
-    u32x4_t qv[QS][2][kPieces];
+    // ACC2 (QS = 3, every NP): the prologue plays Q0 Q1 T0 T1 and step k issues Q(k + 2) (register
+    // slot (k + 2) % 3), then T(k + 2).  A wave's vector-memory operations therefore retire in the
+    // order  Q0 Q1 T0 T1 | Q2 T2 | Q3 T3 | ...  with 2 NP operations per Q group and 2 NP per T
+    // group.  At step k's barrier the operations younger than T(k) are: k = 0: T1; k >= 1: step
+    // k - 1's group, Q(k + 1) and T(k + 1) — each where it exists (Q(j), T(j): j < SS).  So the
+    // wait is vmcnt(2 NP [Q(k + 1)] + 2 NP [T(k + 1)]) = 12 / 8 / 4 in the steady state, 2 NP at
+    // step 0 and at a step whose group held one of the two, 0 at the last.  Q(k) precedes T(k) in
+    // every case (the prologue's Q0 Q1 before T0; step k - 2's Q(k) before its T(k)), so the same
+    // wait retires it.  Slot reuse: T(k + 2) overwrites ring slot (k + 2) % 3 = (k - 1) % 3, last
+    // read in step k - 1, whose ds_reads every wave retired (lgkmcnt(0)) before step k's barrier;
+    // Q(k + 2) overwrites register slot (k - 1) % 3, dead after step k - 1's MFMAs.  None of this
+    // depends on NP but the counts.
+    u32x4_t qv[QS][2][NP];
     auto issue_q = [&](int s, int slot) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int c = 0; c < kPieces; ++c) {
+            for (int c = 0; c < NP; ++c) {
                 if constexpr (VF & 1)
                     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qv[slot][i][c]) : "v"(qsrc + s * qstep + i * kRecU + c * 64) : "memory");
                 else
@@ -321,88 +352,124 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
     // One K step: per map row, its three target fragments (read one row ahead) and 12 MFMAs.
     auto compute = [&](int tslot, int qslot) __attribute__((always_inline)) {
         const u32x4_t *A = reinterpret_cast<const u32x4_t *>(smem + tslot * kSlotBytes);
-        bfx8_t qh[2], qm[2], ql[2];
+        if constexpr (NP == kPieces) {
+            bfx8_t qh[2], qm[2], ql[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            qh[i] = __builtin_bit_cast(bfx8_t, qv[qslot][i][0]);
-            qm[i] = __builtin_bit_cast(bfx8_t, qv[qslot][i][1]);
-            ql[i] = __builtin_bit_cast(bfx8_t, qv[qslot][i][2]);
-        }
-        bfx8_t th[2], tm[2], tl8[2];
-        th[0] = __builtin_bit_cast(bfx8_t, A[lane]);
-        tm[0] = __builtin_bit_cast(bfx8_t, A[64 + lane]);
-        tl8[0] = __builtin_bit_cast(bfx8_t, A[128 + lane]);
-        if constexpr (ACC2) {
+            for (int i = 0; i < 2; ++i) {
+                qh[i] = __builtin_bit_cast(bfx8_t, qv[qslot][i][0]);
+                qm[i] = __builtin_bit_cast(bfx8_t, qv[qslot][i][1]);
+                ql[i] = __builtin_bit_cast(bfx8_t, qv[qslot][i][2]);
+            }
+            bfx8_t th[2], tm[2], tl8[2];
+            th[0] = __builtin_bit_cast(bfx8_t, A[lane]);
+            tm[0] = __builtin_bit_cast(bfx8_t, A[64 + lane]);
+            tl8[0] = __builtin_bit_cast(bfx8_t, A[128 + lane]);
+            if constexpr (ACC2) {
 #pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const int c = r & 1;
-                if (r + 1 < NR) {
-                    th[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 3) * 64 + lane]);
-                    tm[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 4) * 64 + lane]);
-                    tl8[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 5) * 64 + lane]);
+                for (int r = 0; r < NR; ++r) {
+                    const int c = r & 1;
+                    if (r + 1 < NR) {
+                        th[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 3) * 64 + lane]);
+                        tm[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 4) * 64 + lane]);
+                        tl8[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 5) * 64 + lane]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tl8[c], qh[i], acs[i][r], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], ql[i], acs[i][r], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qm[i], acs[i][r], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qh[i], acs[i][r], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qm[i], acs[i][r], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) acc[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qh[i], acc[i][r], 0, 0, 0);
+                }
+                // schedule: row 0's reads, then per row the next row's 3 reads ahead of its 12 MFMAs
+                __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    if (r + 1 < NR) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+                }
+            } else {
+                f32x4_t t[2][2];  // per row: the six products of one K step, summed from zero (row parity)
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const int c = r & 1;
+                    if (r + 1 < NR) {
+                        th[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 3) * 64 + lane]);
+                        tm[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 4) * 64 + lane]);
+                        tl8[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 5) * 64 + lane]);
+                    }
+                    const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tl8[c], qh[i], z, 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], ql[i], t[c][i], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qm[i], t[c][i], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qh[i], t[c][i], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qm[i], t[c][i], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qh[i], t[c][i], 0, 0, 0);
+                    // the previous row's step sum joins its accumulator (one rounding per K step) while
+                    // this row's MFMAs run
+                    if (r > 0) {
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) acc[i][r - 1] += t[c ^ 1][i];
+                    }
                 }
 #pragma unroll
-                for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tl8[c], qh[i], acs[i][r], 0, 0, 0);
+                for (int i = 0; i < 2; ++i) acc[i][NR - 1] += t[(NR - 1) & 1][i];
+                // schedule: row 0's reads, then per row the next row's 3 reads ahead of its 12 MFMAs and
+                // the previous row's 8 accumulator adds behind them
+                __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
 #pragma unroll
-                for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], ql[i], acs[i][r], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qm[i], acs[i][r], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qh[i], acs[i][r], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qm[i], acs[i][r], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) acc[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qh[i], acc[i][r], 0, 0, 0);
-            }
-            // schedule: row 0's reads, then per row the next row's 3 reads ahead of its 12 MFMAs
-            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                if (r + 1 < NR) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+                for (int r = 0; r < NR; ++r) {
+                    if (r + 1 < NR) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+                    if (r > 0) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
             }
         } else {
-            f32x4_t t[2][2];  // per row: the six products of one K step, summed from zero (row parity)
+            // the reduced modes: per map row its NP target fragments (read one row ahead) and the
+            // products among the kept pieces — 6 MFMAs (NP = 2) or 2 (NP = 1)
+            bfx8_t qp[2][NP], tp[2][NP];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int c = 0; c < NP; ++c) qp[i][c] = __builtin_bit_cast(bfx8_t, qv[qslot][i][c]);
+#pragma unroll
+            for (int c = 0; c < NP; ++c) tp[0][c] = __builtin_bit_cast(bfx8_t, A[c * 64 + lane]);
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 const int c = r & 1;
                 if (r + 1 < NR) {
-                    th[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 3) * 64 + lane]);
-                    tm[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 4) * 64 + lane]);
-                    tl8[c ^ 1] = __builtin_bit_cast(bfx8_t, A[(3 * r + 5) * 64 + lane]);
+#pragma unroll
+                    for (int e = 0; e < NP; ++e) tp[c ^ 1][e] = __builtin_bit_cast(bfx8_t, A[(NP * (r + 1) + e) * 64 + lane]);
                 }
-                const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (NP == 2) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tl8[c], qh[i], z, 0, 0, 0);
+                    for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tp[c][1], qp[i][0], acs[i][r], 0, 0, 0);
 #pragma unroll
-                for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], ql[i], t[c][i], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qm[i], t[c][i], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tm[c], qh[i], t[c][i], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qm[i], t[c][i], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) t[c][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[c], qh[i], t[c][i], 0, 0, 0);
-                // the previous row's step sum joins its accumulator (one rounding per K step) while
-                // this row's MFMAs run
-                if (r > 0) {
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) acc[i][r - 1] += t[c ^ 1][i];
+                    for (int i = 0; i < 2; ++i) acs[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tp[c][0], qp[i][1], acs[i][r], 0, 0, 0);
                 }
+#pragma unroll
+                for (int i = 0; i < 2; ++i) acc[i][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tp[c][0], qp[i][0], acc[i][r], 0, 0, 0);
             }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i][NR - 1] += t[(NR - 1) & 1][i];
-            // schedule: row 0's reads, then per row the next row's 3 reads ahead of its 12 MFMAs and
-            // the previous row's 8 accumulator adds behind them
-            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+            // schedule: row 0's reads, then per row the next row's NP reads ahead of its MFMAs
+            constexpr int kMfmaPerRow = NP == 2 ? 6 : 2;
+            __builtin_amdgcn_sched_group_barrier(0x100, NP, 0);
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
-                if (r + 1 < NR) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
-                if (r > 0) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+                if (r + 1 < NR) __builtin_amdgcn_sched_group_barrier(0x100, NP, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, kMfmaPerRow, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
         }
     };
 
@@ -416,7 +483,8 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
 #pragma unroll
         for (int s = 0; s < SS; ++s) {
             // operations younger than T(s): at step 0 the prologue's [Q2,] T1; else step s - 1's
-            // group Q(s - 1 + QD), T(s + 1) — where they exist
+            // group Q(s - 1 + QD), T(s + 1) — where they exist.  (kQLoads and DPW are both 2 NP, so
+            // the two one-group cases below name the same wait.)
             const int younger = s == 0 ? (QD > 2 && SS > 2 ? kQLoads : 0) + (SS > 1 ? DPW : 0)
                                        : (s - 1 + QD < SS ? kQLoads : 0) + (s + 1 < SS ? DPW : 0);
             if (younger == kQLoads + DPW) wait_vmcnt_barrier<kQLoads + DPW>();
@@ -425,8 +493,11 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
             else wait_vmcnt_barrier<0>();
             const int qs = s % QS;
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-                asm volatile("" : "+v"(qv[qs][i][0]), "+v"(qv[qs][i][1]), "+v"(qv[qs][i][2]));
+            for (int i = 0; i < 2; ++i) {
+                if constexpr (NP == 3) asm volatile("" : "+v"(qv[qs][i][0]), "+v"(qv[qs][i][1]), "+v"(qv[qs][i][2]));
+                else if constexpr (NP == 2) asm volatile("" : "+v"(qv[qs][i][0]), "+v"(qv[qs][i][1]));
+                else asm volatile("" : "+v"(qv[qs][i][0]));
+            }
             if (s + QD < SS) issue_q(s + QD, (s + QD) % QS);
             if (s + 2 < SS) issue_t(s + 2, (s + 2) % kRing);
             if (qact) compute(s % kRing, qs);  // a wave whose queries all lie past NQ skips its MFMAs
@@ -472,8 +543,9 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
     // (4 (rp >> 2) + grp, 4 (rp & 3) + c) of query block i — the level-0 store operand as it
     // stands.  split_sum differs from hi + lo only where hi is infinite, so the wave takes the
     // per-element form only when one of its accumulators is (fmaxf drops a NaN operand, and a NaN
-    // hi gives a NaN sum either way); rows >= NR are zero on both paths.
-    if constexpr (ACC2) {
+    // hi gives a NaN sum either way); rows >= NR are zero on both paths.  NP = 1 has the one
+    // accumulator.
+    if constexpr (ACC2 && NP > 1) {
         float big = 0.f;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -596,16 +668,16 @@ __device__ __forceinline__ void build_tile(const Args &p, const Tile tl) {
     else pool_store(std::true_type{});
 }
 
-template <int SS, bool ACC2 = true, int VF = 0, bool FAST = false>
+template <int SS, bool ACC2 = true, int VF = 0, bool FAST = false, int NP = kPieces>
 __global__ __launch_bounds__(256, 2) void corr_build_bf16_kernel(Args p) {
     const int t = xcd_swizzle(blockIdx.x, gridDim.x);
     Tile tl = p.order == 2 ? xcd_block_tile(p, t) : patch_tile(t, p.npatch, p.NQG, p.CB, p.order, p.gq);
     tl.py += p.py0;
     // two whole code paths (no value flows out of either): a half patch runs half the MFMAs
     if (!(VF & 4) && SS > 0 && tl.py * kPatchRows + kPatchRows / 2 >= p.H)
-        build_tile<SS, kPatchRows / 2, ACC2, VF, FAST>(p, tl);
+        build_tile<SS, kPatchRows / 2, ACC2, VF, FAST, NP>(p, tl);
     else
-        build_tile<SS, kPatchRows, ACC2, VF, FAST>(p, tl);
+        build_tile<SS, kPatchRows, ACC2, VF, FAST, NP>(p, tl);
 }
 
 struct Ws {
@@ -623,20 +695,34 @@ inline Ws workspace_of(void *ws, int B, const Geom &g) {
 
 constexpr int kLibVF = 2;  // the library's VF: K loop at priority 1
 
-template <int SS, bool ACC2 = true, int VF = kLibVF>
+template <int SS, bool ACC2 = true, int VF = kLibVF, int NP = kPieces>
 hipError_t launch_kernel(dim3 grid, const Args &p, hipStream_t s) {
+    constexpr int kLds = lds_bytes(NP);
     const bool fast = p.nlev == 4;
     static std::atomic<unsigned long long> lds_done[2];
-    const void *fn = fast ? (const void *)corr_build_bf16_kernel<SS, ACC2, VF, true>
-                          : (const void *)corr_build_bf16_kernel<SS, ACC2, VF, false>;
+    const void *fn = fast ? (const void *)corr_build_bf16_kernel<SS, ACC2, VF, true, NP>
+                          : (const void *)corr_build_bf16_kernel<SS, ACC2, VF, false, NP>;
     const hipError_t e = ensure_lds_limit(fn, kLds, lds_done[fast]);
     if (e != hipSuccess) return e;
     const dim3 blk(256);
     if (fast)
-        hipLaunchKernelGGL((corr_build_bf16_kernel<SS, ACC2, VF, true>), grid, blk, kLds, s, p);
+        hipLaunchKernelGGL((corr_build_bf16_kernel<SS, ACC2, VF, true, NP>), grid, blk, kLds, s, p);
     else
-        hipLaunchKernelGGL((corr_build_bf16_kernel<SS, ACC2, VF, false>), grid, blk, kLds, s, p);
+        hipLaunchKernelGGL((corr_build_bf16_kernel<SS, ACC2, VF, false, NP>), grid, blk, kLds, s, p);
     return hipGetLastError();
+}
+
+// The reduced modes' kernel for S K steps (the specialised K loop for S <= 8, else the generic).
+template <int NP>
+hipError_t launch_reduced(int S, dim3 grid, const Args &p, hipStream_t s) {
+    switch (S <= 8 ? S : 0) {
+#define CORR_BF16_CASE(c) \
+    case c: return launch_kernel<c, true, kLibVF, NP>(grid, p, s);
+        CORR_BF16_CASE(0) CORR_BF16_CASE(1) CORR_BF16_CASE(2) CORR_BF16_CASE(3) CORR_BF16_CASE(4)
+        CORR_BF16_CASE(5) CORR_BF16_CASE(6) CORR_BF16_CASE(7) CORR_BF16_CASE(8)
+#undef CORR_BF16_CASE
+        default: return hipErrorInvalidValue;
+    }
 }
 
 
@@ -652,7 +738,8 @@ size_t workspace_bytes(int B, int D, int NQ, int H, int W) {
 // (train B8 15.4 -> 14.0 us, MVSEC B16 29.9 -> 27.7 us), else 1 (DSEC's 4,800 records: 6.3 us
 // with one, 8.5 with four — a single round of workgroups, profiles/r06g_kbench_pack_rpw.txt).
 hipError_t launch_pack(const float *f1, int NQ, const float *f2, int B, int D, int H, int W, void *ws,
-                       hipStream_t s, int y0 = 0, int y1 = -1, bool pack_q = true, int rpw = 0) {
+                       hipStream_t s, int y0 = 0, int y1 = -1, bool pack_q = true, int rpw = 0, int precision = 0) {
+    if (!precision_supported(precision)) return hipErrorInvalidValue;
     if (y1 < 0) y1 = H;
     const Geom g = geom(D, NQ, H, W);
     const Ws w = workspace_of(ws, B, g);
@@ -668,6 +755,18 @@ hipError_t launch_pack(const float *f1, int NQ, const float *f2, int B, int D, i
     const int recs = g.S * std::max(pack_q ? a.nblk[0] : 0, a.nblk[1]);
     if (rpw == 0) rpw = (long)recs * B * (pack_q ? 2 : 1) >= 8192 ? 4 : 1;
     const dim3 blk(256);
+    if (precision != 0) {
+        // a reduced mode stores the kept pieces only (records per wave: 4 or 1, by size as above)
+        const dim3 grid((unsigned)(rpw == 4 ? (recs + 15) / 16 : (recs + 3) / 4), B, pack_q ? 2 : 1);
+        if (precision == 1) {
+            if (rpw == 4) hipLaunchKernelGGL((bf16_pack_kernel<4, 2>), grid, blk, 0, s, a);
+            else hipLaunchKernelGGL((bf16_pack_kernel<1, 2>), grid, blk, 0, s, a);
+        } else {
+            if (rpw == 4) hipLaunchKernelGGL((bf16_pack_kernel<4, 1>), grid, blk, 0, s, a);
+            else hipLaunchKernelGGL((bf16_pack_kernel<1, 1>), grid, blk, 0, s, a);
+        }
+        return hipGetLastError();
+    }
     if (rpw == 4)
         hipLaunchKernelGGL(bf16_pack_kernel<4>, dim3((unsigned)((recs + 15) / 16), B, pack_q ? 2 : 1), blk, 0, s, a);
     else if (rpw == 2)
@@ -683,7 +782,9 @@ hipError_t launch_pack(const float *f1, int NQ, const float *f2, int B, int D, i
 // y0, y1: the target region (as launch_pack), whose pyramid rows [y0 >> l, ceil(y1 / 2^l)) of
 // every level it writes.
 hipError_t launch_mfma(int NQ, int B, int D, int H, int W, int levels, const LevelPtrs &pyr, void *ws,
-                       hipStream_t s, int variant = 0, int order = 1, int y0 = 0, int y1 = -1, int gq = 0) {
+                       hipStream_t s, int variant = 0, int order = 1, int y0 = 0, int y1 = -1, int gq = 0,
+                       int precision = 0) {
+    if (!precision_supported(precision) || (precision != 0 && variant != 0)) return hipErrorInvalidValue;
     if (y1 < 0) y1 = H;
     const Geom g = geom(D, NQ, H, W);
     const Ws w = workspace_of(ws, B, g);
@@ -723,6 +824,10 @@ hipError_t launch_mfma(int NQ, int B, int D, int H, int W, int levels, const Lev
             case 6: e = launch_kernel<8, true, 0>(grid, p, s); break;
             default: return hipErrorInvalidValue;
         }
+    } else if (precision == 1) {
+        e = launch_reduced<2>(g.S, grid, p, s);
+    } else if (precision == 2) {
+        e = launch_reduced<1>(g.S, grid, p, s);
     } else switch (g.S <= 8 ? g.S : 0) {
 #define CORR_BF16_CASE(c) \
     case c: e = launch_kernel<c>(grid, p, s); break;
@@ -743,23 +848,24 @@ size_t build_bf16_workspace(int B, int D, int NQ, int H, int W) {
 }
 
 // part: 0 = pack + MFMA; 1 = the pack alone; 2 = the MFMA kernel alone (measurement: the
-// workspace must already hold this pair's pack).
+// workspace must already hold this pair's pack).  precision: CORR_PREC_* — the pieces the pack
+// stores and the kernel stages and multiplies (0: all three, the build as it always was).
 hipError_t launch_build_bf16(const float *f1, int NQ, const float *f2, int B, int D, int H, int W, int levels,
-                             const LevelPtrs &pyr, void *ws, hipStream_t s, int part) {
+                             const LevelPtrs &pyr, void *ws, hipStream_t s, int part, int precision) {
     if (part != 2) {
-        const hipError_t e = bf16b::launch_pack(f1, NQ, f2, B, D, H, W, ws, s);
+        const hipError_t e = bf16b::launch_pack(f1, NQ, f2, B, D, H, W, ws, s, 0, -1, true, 0, precision);
         if (e != hipSuccess || part == 1) return e;
     }
-    return bf16b::launch_mfma(NQ, B, D, H, W, levels, pyr, ws, s);
+    return bf16b::launch_mfma(NQ, B, D, H, W, levels, pyr, ws, s, 0, 1, 0, -1, 0, precision);
 }
 
 // One target region [y0, y1) of the build (corr_build_region): f2_rows holds those fmap2 rows.
 hipError_t launch_build_bf16_region(const float *f1, int NQ, const float *f2_rows, int y0, int y1, int B, int D,
                                     int H, int W, int levels, const LevelPtrs &pyr, void *ws, bool pack_q,
-                                    hipStream_t s) {
-    const hipError_t e = bf16b::launch_pack(f1, NQ, f2_rows, B, D, H, W, ws, s, y0, y1, pack_q);
+                                    hipStream_t s, int precision) {
+    const hipError_t e = bf16b::launch_pack(f1, NQ, f2_rows, B, D, H, W, ws, s, y0, y1, pack_q, 0, precision);
     if (e != hipSuccess) return e;
-    return bf16b::launch_mfma(NQ, B, D, H, W, levels, pyr, ws, s, 0, 1, y0, y1);
+    return bf16b::launch_mfma(NQ, B, D, H, W, levels, pyr, ws, s, 0, 1, y0, y1, 0, precision);
 }
 
 }  // namespace corr

@@ -150,10 +150,10 @@ hipError_t launch_build_split(const float *f1, int NQ, const float *f2, int B, i
 // The bf16 three-piece build (corr_build_bf16.hip): pack kernel + bf16 MFMA kernel.
 size_t build_bf16_workspace(int B, int D, int NQ, int H, int W);
 hipError_t launch_build_bf16(const float *f1, int NQ, const float *f2, int B, int D, int H, int W, int levels,
-                             const LevelPtrs &pyr, void *ws, hipStream_t s, int part = 0);
+                             const LevelPtrs &pyr, void *ws, hipStream_t s, int part = 0, int precision = 0);
 hipError_t launch_build_bf16_region(const float *f1, int NQ, const float *f2_rows, int y0, int y1, int B, int D,
                                     int H, int W, int levels, const LevelPtrs &pyr, void *ws, bool pack_q,
-                                    hipStream_t s);
+                                    hipStream_t s, int precision = 0);
 // Ordered split-K sum + 1/sqrt(D) of [splits][per] partial slabs into C (corr_bwd.hip).
 // fix: the bf16x6 GEMMs' NaN recompute (NanFix), or null.
 hipError_t launch_splitk_reduce(const float *ws, float *C, int splits, size_t per, float sD, hipStream_t s,

@@ -47,6 +47,8 @@ TRAIN_EXPORTS = ("corr_upsample_loss_workspace", "corr_upsample_loss", "corr_ups
                  "corr_sequence_loss_workspace", "corr_sequence_loss", "corr_sequence_loss_bwd")
 # include/corr_mi355x_enc_prec.h: the encoders' convolutions in a precision mode
 ENC_PREC_EXPORTS = ("corr_enc_conv_forward_prec", "corr_enc_stem_forward_prec", "corr_enc_pw_forward_prec")
+# include/corr_mi355x_build_prec.h: the all-pairs build in a precision mode
+BUILD_PREC_EXPORTS = ("corr_build_ex_prec", "corr_build_region_prec")
 # include/corr_mi355x_train_head.h: the fused loss with the mask head inside the launch
 TRAIN_HEAD_EXPORTS = ("corr_mask_upsample_loss_workspace", "corr_mask_upsample_loss", "corr_mask_upsample_loss_bwd")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
@@ -192,6 +194,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_enc_conv_forward_prec.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, sz, i, vp]
     lib.corr_enc_stem_forward_prec.argtypes = [vp, i, i, i, i, vp, vp, i, vp, vp, sz, i, vp]
     lib.corr_enc_pw_forward_prec.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, sz, i, vp]
+    lib.corr_build_ex_prec.argtypes = [i, vp, i, vp, i, i, i, i, i, vp, vp, sz, i, vp]
+    lib.corr_build_region_prec.argtypes = [i, vp, i, vp, i, i, i, i, i, i, i, vp, vp, sz, i, i, vp]
     fl = ctypes.c_float
     lib.corr_upsample_loss_workspace.argtypes, lib.corr_upsample_loss_workspace.restype = [i, i, i], sz
     lib.corr_upsample_loss.argtypes = [vp, vp, vp, vp, i, i, i, i, i, fl, i, vp, vp, sz, vp]
@@ -205,7 +209,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
                                                 sz, vp]
     for f in ("corr_upsample_loss", "corr_upsample_loss_bwd", "corr_sequence_loss", "corr_sequence_loss_bwd",
               "corr_mask_upsample_loss", "corr_mask_upsample_loss_bwd",
-              "corr_gru_half_step_prec", "corr_conv_forward_prec", *ENC_PREC_EXPORTS):
+              "corr_gru_half_step_prec", "corr_conv_forward_prec", *ENC_PREC_EXPORTS, *BUILD_PREC_EXPORTS):
         getattr(lib, f).restype = i
     for f in ("corr_ondemand_lookup_conv", "corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
               "corr_flow_head_forward", "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
@@ -385,10 +389,11 @@ def build_workspace(fmap1, fmap2, algo=None):
     return torch.empty(n, dtype=torch.uint8, device=fmap1.device)
 
 
-def build(fmap1, fmap2, levels, algo=None, workspace=None):
-    """corr_build_ex into caller-allocated tiled levels (corr._alloc_pyramid).  fmap1 may be a row
+def build(fmap1, fmap2, levels, algo=None, workspace=None, precision=0):
+    """corr_build_ex_prec into caller-allocated tiled levels (corr._alloc_pyramid).  fmap1 may be a row
     slab [B, D, rows, W] of the query map; fmap2 is the full target map [B, D, H, W].
-    algo: BUILD_BF16X6 (default, see default_algo), BUILD_F16X3 or BUILD_FP32."""
+    algo: BUILD_BF16X6 (default, see default_algo), BUILD_F16X3 or BUILD_FP32.  precision: a
+    CORR_PREC_* value (precision.code); a reduced one needs BUILD_BF16X6."""
     algo = default_algo() if algo is None else algo
     B, D, H, W = fmap2.shape
     a, b, pp = _dev(fmap1, "fmap1"), _dev(fmap2, "fmap2"), _ptrs(levels, "pyr")
@@ -398,25 +403,27 @@ def build(fmap1, fmap2, levels, algo=None, workspace=None):
     wp = 0 if workspace is None else workspace.data_ptr()
     wn = 0 if workspace is None else workspace.numel() * workspace.element_size()
     with torch.cuda.device(fmap1.device):
-        _check(load().corr_build_ex(algo, a, _nq(fmap1), b, B, D, H, W, len(levels), pp, wp, wn,
-                                    _stream(fmap1)))
+        _check(load().corr_build_ex_prec(algo, a, _nq(fmap1), b, B, D, H, W, len(levels), pp, wp, wn,
+                                         int(precision), _stream(fmap1)))
 
 
 REGION_PACK_QUERIES = 1
 
 
-def build_region(fmap1, fmap2_rows, y0, y1, H, levels, workspace, pack_queries, algo=BUILD_BF16X6):
-    """corr_build_region: the pyramid entries of target rows [y0, y1) (tiled levels, corr._alloc_pyramid)
-    from fmap2_rows [B, D, y1 - y0, W]; workspace from build_workspace(fmap1, <full fmap2 shape>)."""
+def build_region(fmap1, fmap2_rows, y0, y1, H, levels, workspace, pack_queries, algo=BUILD_BF16X6, precision=0):
+    """corr_build_region_prec: the pyramid entries of target rows [y0, y1) (tiled levels, corr._alloc_pyramid)
+    from fmap2_rows [B, D, y1 - y0, W]; workspace from build_workspace(fmap1, <full fmap2 shape>).
+    precision: a CORR_PREC_* value, the same for every region call of one build."""
     B, D, rows, W = fmap2_rows.shape
     if rows != y1 - y0:
         raise ValueError(f"fmap2_rows has {rows} rows for the region [{y0}, {y1})")
     a, b, pp = _dev(fmap1, "fmap1"), _dev(fmap2_rows, "fmap2_rows"), _ptrs(levels, "pyr")
     _check_levels(levels, B * _nq(fmap1), H, W, "pyr")
     with torch.cuda.device(fmap1.device):
-        _check(load().corr_build_region(algo, a, _nq(fmap1), b, y0, y1, B, D, H, W, len(levels), pp,
-                                        workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                        REGION_PACK_QUERIES if pack_queries else 0, _stream(fmap1)))
+        _check(load().corr_build_region_prec(algo, a, _nq(fmap1), b, y0, y1, B, D, H, W, len(levels), pp,
+                                             workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                             REGION_PACK_QUERIES if pack_queries else 0, int(precision),
+                                             _stream(fmap1)))
 
 
 def lookup(levels, coords, radius, out, H=None, W=None):

@@ -21,9 +21,11 @@ avg-pool backward folded into level 0 in one pass, and the two MFMA GEMMs.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
-from . import _lib
+from . import _lib, precision as _precision
 from ._cache import cached
 
 
@@ -279,10 +281,29 @@ class _CorrFn(torch.autograd.Function):
         return (df1 if ctx.needs_input_grad[0] else None, df2 if ctx.needs_input_grad[1] else None)
 
 
-class CorrBlock:
-    """MI355X-native replacement for model/corr.py:12 ``CorrBlock``."""
+def _build_precision(precision, trains: bool) -> str:
+    """The mode name a CorrBlock's build runs in: `precision` (None: ERAFT_AMD_CORR_PRECISION, else
+    "bf16x6"); an unknown name raises; "bf16x6" when the build is recorded for autograd (the modes
+    are inference-only).  A reduced mode that would run exists on the bf16 MFMA build alone: with
+    ERAFT_AMD_BUILD=fp32 / f16x3 it raises."""
+    name = _precision.resolve_corr(None) if precision is None else precision
+    reduced = _precision.code(name) != _precision.BF16X6
+    if trains or not reduced:
+        return _precision.DEFAULT
+    if _lib.default_algo() != _lib.BUILD_BF16X6:
+        raise ValueError(f"corr precision {name!r} needs the bf16x6 build (ERAFT_AMD_BUILD is "
+                         f"{os.environ.get('ERAFT_AMD_BUILD')!r})")
+    return name
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+
+class CorrBlock:
+    """MI355X-native replacement for model/corr.py:12 ``CorrBlock``.
+
+    precision: the build's mode, "bf16x6" (default), "bf16x3" or "bf16" (precision.py); None reads
+    ERAFT_AMD_CORR_PRECISION.  The attribute `precision` holds the mode that ran: "bf16x6" whenever
+    the build is recorded for autograd.  The lookups work on whatever values the pyramid holds."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, precision=None):
         self.num_levels = num_levels
         self.radius = radius
         if not (0 <= radius <= _lib.MAX_RADIUS):
@@ -296,13 +317,16 @@ class CorrBlock:
         self._view = None  # corr_pyramid's exported levels, made on first access ...
         self._view_grad = False  # ... with (True) or without autograd
         self._assigned = False  # corr_pyramid was assigned: later lookups carry no gradient
-        if torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad):
+        trains = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
+        self.precision = _build_precision(precision, trains)
+        if trains:
             self._token = _BuildFn.apply(fmap1, fmap2, num_levels, self._state)
             self._state.trains = True
         else:
             B = fmap1.shape[0]
             self._state.levels = _alloc_pyramid(B, H, W, num_levels, fmap1)
-            _lib.build(fmap1.detach(), fmap2.detach(), self._state.levels)
+            _lib.build(fmap1.detach(), fmap2.detach(), self._state.levels,
+                       precision=_precision.code(self.precision))
 
     @property
     def corr_pyramid(self):

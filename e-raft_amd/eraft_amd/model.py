@@ -20,7 +20,8 @@ import torch.nn.functional as F
 
 from .corr import CorrBlock
 from .ondemand import OnDemandConvCorrBlock, OnDemandCorrBlock
-from .precision import DEFAULT as _PRECISION, resolve as _resolve_precision, resolve_encoder as _resolve_encoder_precision
+from .precision import (DEFAULT as _PRECISION, resolve as _resolve_precision, resolve_corr as _resolve_corr_precision,
+                        resolve_encoder as _resolve_encoder_precision)
 from .utils import coords_grid
 
 
@@ -365,10 +366,11 @@ class ERAFT(nn.Module):
     # mask is neither stored nor saved for backward.  Default off (DESIGN §32 has the measurements).
     fuse_mask_loss = os.environ.get("ERAFT_AMD_FUSE_MASK_LOSS", "0") == "1"
     # The precision mode of the GRU and the update block's 3x3 convolutions ("bf16x6", "bf16x3" or
-    # "bf16": precision.py), and that of the two encoders' convolutions; an instance takes each from
-    # its config (below).
+    # "bf16": precision.py), that of the two encoders' convolutions and that of the correlation
+    # build; an instance takes each from its config (below).
     precision = _PRECISION
     encoder_precision = _PRECISION
+    corr_precision = _PRECISION
 
     def __init__(self, config, n_first_channels):
         super().__init__()
@@ -399,10 +401,18 @@ class ERAFT(nn.Module):
         #   and head), where encoder.encoder_forward runs (ERAFT_AMD_FUSE_ENCODER=1).
         # Both act at inference only; the torch paths and training stay fp32.  convf1, the flow
         # head's second convolution, the mask head and the lookup with convc1 stay "bf16x6".
+        # A third knob is the correlation build's own:
+        #   `corr_precision` (the same values), overridden by ERAFT_AMD_CORR_PRECISION=<name>, reaches
+        #   CorrBlock's all-pairs build (the lookups read whatever values it left in the pyramid).
+        # The reference casts the feature maps to fp32 before its CorrBlock, outside the autocast, so
+        # `mixed_precision` does not set it.  Inference only: a build recorded for autograd runs
+        # "bf16x6" (CorrBlock.precision tells).  With `alternate_corr` the on-demand blocks compute
+        # their windows on the fp32 MFMA and ignore it.
         self.precision = _resolve_precision(config)
         self.update_block.precision = self.update_block.gru.precision = self.precision
         self.encoder_precision = _resolve_encoder_precision(config)
         self.fnet.precision = self.cnet.precision = self.encoder_precision
+        self.corr_precision = _resolve_corr_precision(config)
 
     def freeze_bn(self):
         for m in self.modules():
@@ -451,7 +461,10 @@ class ERAFT(nn.Module):
             corr_fn = block(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius,
                             train=torch.is_grad_enabled())
         else:
-            corr_fn = CorrBlock(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius)
+            # (the default mode is passed by omission: a drop-in class with the reference's signature works)
+            mode = {} if self.corr_precision == _PRECISION else {"precision": self.corr_precision}
+            corr_fn = CorrBlock(fmap1.float(), fmap2.float(), num_levels=self.corr_levels, radius=self.corr_radius,
+                                **mode)
         net, inp = torch.split(self.cnet(image2), [self.hidden_dim, self.context_dim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)
         n, _, h, w = image1.shape

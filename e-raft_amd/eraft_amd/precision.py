@@ -1,5 +1,6 @@
-"""The precision modes of the convolution kernels (include/corr_mi355x.h: CORR_PREC_*), the
-counterpart of the reference's mixed_precision (model/eraft.py:31,102-133).
+"""The precision modes of the convolution kernels and of the correlation build
+(include/corr_mi355x.h: CORR_PREC_*), the counterpart of the reference's mixed_precision
+(model/eraft.py:31,102-133).
 
 A mode names the pieces of the exact three-piece bf16 split that a kernel keeps of both operands:
 
@@ -7,7 +8,7 @@ A mode names the pieces of the exact three-piece bf16 split that a kernel keeps 
   "bf16x3"  hi, mid: three products, operands to 2^-18 and the dropped mid x mid to 2^-16 relative
   "bf16"    hi: one product, operands to 2^-9 relative
 
-Accumulation is fp32 in every mode.  Two knobs choose a mode, each for its own layers:
+Accumulation is fp32 in every mode.  Three knobs choose a mode, each for its own layers:
 
   `mixed_precision` / ERAFT_AMD_PRECISION (resolve)
       the fused GRU half steps (the eight convolutions of SepConvGRU) and the update block's fused
@@ -18,11 +19,18 @@ Accumulation is fp32 in every mode.  Two knobs choose a mode, each for its own l
       residual stages, the two 1x1 projections and the 1x1 head), where encoder.encoder_forward runs:
       inference with ERAFT_AMD_FUSE_ENCODER=1 on fp32 GPU tensors.  A piece that encoder.USE_KERNEL
       leaves on torch stays fp32.
+  `corr_precision` / ERAFT_AMD_CORR_PRECISION (resolve_corr)
+      the all-pairs correlation build of CorrBlock (the bf16 MFMA build, ERAFT_AMD_BUILD unset or
+      bf16x6), at inference.  The reference casts both feature maps to fp32 before CorrBlock,
+      outside its autocast (model/eraft.py:106-108), so `mixed_precision` does NOT switch this on:
+      only its own key and variable do.  A build recorded for autograd runs "bf16x6"; the
+      on-demand blocks (no all-pairs volume) use the fp32 MFMA and ignore it.
 
 The reference's single switch wraps the encoders and the update block in one autocast, so it
-corresponds to setting both.  The torch paths and training stay fp32 and ignore both; convf1, the
-flow head's second convolution, the mask head with the upsampling and the lookup with convc1 stay
-"bf16x6" under either.
+corresponds to setting the first two.  The torch paths and training stay fp32 and ignore all
+three; convf1, the flow head's second convolution, the mask head with the upsampling and the
+lookup with convc1 stay "bf16x6" under any of them (the lookups read whatever values the build
+left in the pyramid).
 """
 from __future__ import annotations
 
@@ -33,6 +41,7 @@ MODES = {"bf16x6": BF16X6, "bf16x3": BF16X3, "bf16": BF16}
 DEFAULT = "bf16x6"
 ENV = "ERAFT_AMD_PRECISION"
 ENCODER_ENV = "ERAFT_AMD_ENCODER_PRECISION"
+CORR_ENV = "ERAFT_AMD_CORR_PRECISION"
 
 
 def code(name) -> int:
@@ -71,3 +80,11 @@ def resolve_encoder(config=None) -> str:
     ERAFT_AMD_ENCODER_PRECISION=<name>; a variable that is set but empty counts as unset, any other
     unknown name raises.  Independent of `mixed_precision`."""
     return _resolve(config, "encoder_precision", ENCODER_ENV)
+
+
+def resolve_corr(config=None) -> str:
+    """The mode name of a model's correlation build: the config key `corr_precision` (absent, None or
+    False: "bf16x6"; True: "bf16x3"; a string: that mode), overridden by
+    ERAFT_AMD_CORR_PRECISION=<name>; a variable that is set but empty counts as unset, any other
+    unknown name raises.  Independent of `mixed_precision` and `encoder_precision`."""
+    return _resolve(config, "corr_precision", CORR_ENV)

@@ -31,8 +31,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import _lib
-from .corr import _alloc_grad_pyramid, _alloc_pyramid
+from . import _lib, precision as _precision
+from .corr import _alloc_grad_pyramid, _alloc_pyramid, _build_precision
 
 
 def row_partition(H: int, world: int, rank: int):
@@ -46,11 +46,11 @@ class HipRows:
     """Row-slab compute on the MI355X kernels (the only production backend)."""
 
     @staticmethod
-    def build(f1_rows, f2, num_levels):
+    def build(f1_rows, f2, num_levels, precision=0):
         B, _, rows, W = f1_rows.shape
         _, _, H, _ = f2.shape
         levels = _alloc_pyramid_rows(B, rows * W, H, W, num_levels, f2)
-        _lib.build(f1_rows, f2, levels)
+        _lib.build(f1_rows, f2, levels, precision=precision)
         return levels
 
     # target-row regions of one build (the chunked broadcast): allocate, then build region by region
@@ -71,8 +71,8 @@ class HipRows:
         return levels, _lib.build_workspace(f1_rows, tuple(f2_shape), _lib.BUILD_BF16X6)
 
     @staticmethod
-    def build_region(f1_rows, f2_chunk, y0, y1, H, levels, ws, first):
-        _lib.build_region(f1_rows, f2_chunk, y0, y1, H, levels, ws, first)
+    def build_region(f1_rows, f2_chunk, y0, y1, H, levels, ws, first, precision=0):
+        _lib.build_region(f1_rows, f2_chunk, y0, y1, H, levels, ws, first, precision=precision)
 
     @staticmethod
     def lookup(levels, coords_rows, radius, H, W):
@@ -118,11 +118,13 @@ def chunk_bounds(H: int, chunks: int):
     return [(y, min(H, y + step)) for y in range(0, H, step)]
 
 
-def _broadcast_build_chunked(backend, f1_rows, fmap2, num_levels, bounds, src, group, rank):
+def _broadcast_build_chunked(backend, f1_rows, fmap2, num_levels, bounds, src, group, rank, precision=0):
     """Broadcast rank src's fmap2 as target-row chunks (all issued asynchronously, in order) and
     build each chunk's pyramid rows as soon as it has arrived; non-source ranks also assemble the
     chunks into fmap2 (the broadcast's contract: fmap2 ends as rank src's map everywhere).
-    Returns the pyramid levels of this rank's query slab."""
+    Returns the pyramid levels of this rank's query slab.  precision: the build's CORR_PREC_*
+    value, one for every region (a reduced one reaches the backend as a keyword: HipRows only)."""
+    prec = {"precision": precision} if precision else {}
     B, D, H, W = fmap2.shape
     with torch.no_grad():
         bufs = [fmap2.new_empty((B, D, y1 - y0, W)) for y0, y1 in bounds]
@@ -134,7 +136,7 @@ def _broadcast_build_chunked(backend, f1_rows, fmap2, num_levels, bounds, src, g
         for k, ((y0, y1), buf, work) in enumerate(zip(bounds, bufs, works)):
             work.wait()  # RCCL: the compute stream waits on chunk k only; chunk k+1 keeps arriving
             if f1_rows.shape[2] > 0:
-                backend.build_region(f1_rows, buf, y0, y1, H, levels, ws, k == 0)
+                backend.build_region(f1_rows, buf, y0, y1, H, levels, ws, k == 0, **prec)
             if rank != src:
                 fmap2[:, :, y0:y1].copy_(buf)
     return levels
@@ -344,7 +346,7 @@ class RowShardedCorrBlock:
         return PendingFmap2(fmap2, work)
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, group=None, src=0,
-                 fmap1_is_slab=False, backend=HipRows, broadcast=True, chunks=0):
+                 fmap1_is_slab=False, backend=HipRows, broadcast=True, chunks=0, precision=None):
         self.num_levels, self.radius = num_levels, radius
         self.group = group
         self.world = dist.get_world_size(group)
@@ -381,7 +383,15 @@ class RowShardedCorrBlock:
                              f"{self.h1 - self.h0}")
         self.fmap2 = fmap2
         self._token = None
-        if torch.is_grad_enabled() and (f1.requires_grad or fmap2.requires_grad):
+        # the build's precision mode (CorrBlock's rules: None reads ERAFT_AMD_CORR_PRECISION, a build
+        # recorded for autograd runs "bf16x6"); the reduced modes exist on the HIP backend alone
+        trains = torch.is_grad_enabled() and (f1.requires_grad or fmap2.requires_grad)
+        self.precision = _build_precision(precision, trains)
+        prec = _precision.code(self.precision)
+        if prec != _precision.BF16X6 and not (isinstance(backend, type) and issubclass(backend, HipRows)):
+            raise ValueError(f"corr precision {self.precision!r} needs the HipRows backend")
+        pkw = {"precision": prec} if prec else {}
+        if trains:
             # training: autograd through the slab; gradients all-reduced over `group` (module doc)
             st = _ShardState()
             st.B, st.NQ, st.H, st.W = B, (self.h1 - self.h0) * W, H, W
@@ -395,10 +405,11 @@ class RowShardedCorrBlock:
             self._levels = st.levels if self.h1 > self.h0 else None
             return
         if chunked:
-            lv = _broadcast_build_chunked(backend, f1.contiguous(), fmap2, num_levels, bounds, src, group, self.rank)
+            lv = _broadcast_build_chunked(backend, f1.contiguous(), fmap2, num_levels, bounds, src, group, self.rank,
+                                          precision=prec)
             self._levels = lv if self.h1 > self.h0 else None
         else:
-            self._levels = (backend.build(f1.contiguous(), fmap2, num_levels)
+            self._levels = (backend.build(f1.contiguous(), fmap2, num_levels, **pkw)
                             if self.h1 > self.h0 else None)
 
     @property
