@@ -12,6 +12,7 @@
 
 #include "../../include/corr_mi355x_build_prec.h"
 #include "../../include/corr_mi355x_enc_prec.h"
+#include "../../include/corr_mi355x_pw_prec.h"
 #include "../../include/corr_mi355x_train.h"
 #include "../../include/corr_mi355x_train_head.h"
 #include "corr_common.h"
@@ -518,12 +519,15 @@ int corr_lookup_conv_weights(const float *weight, int out_channels, int in_chann
     return hip_status(launch_lookup_conv_weights(weight, out_channels, in_channels, packed, (hipStream_t)stream), fn);
 }
 
-int corr_lookup_conv(const float *const *pyr, const float *coords, int B, int H, int W, int levels, int radius,
-                     const void *packed_weight, const float *bias, int relu, float *out, void *stream) {
-    static const char *fn = "corr_lookup_conv";
+static int check_precision(const char *fn, int precision);
+
+static int lookup_conv(const char *fn, const float *const *pyr, const float *coords, int B, int H, int W, int levels,
+                       int radius, const void *packed_weight, const float *bias, int relu, float *out, void *stream,
+                       int precision) {
     g_err[0] = 0;
-    int rc = check_dims(fn, B, H * W, H, W, levels);
-    if (rc) return rc;
+    int rc;
+    if ((rc = check_precision(fn, precision))) return rc;
+    if ((rc = check_dims(fn, B, H * W, H, W, levels))) return rc;
     if (radius != 4 || levels > 4)
         return fail(CORR_EUNSUPPORTED, "%s: built for radius 4 and <= 4 levels (got %d, %d)", fn, radius, levels);
     ConstLevelPtrs lp{};
@@ -532,8 +536,22 @@ int corr_lookup_conv(const float *const *pyr, const float *coords, int B, int H,
         (rc = check_ptr(fn, bias, "bias")) || (rc = check_ptr(fn, out, "out")))
         return rc;
     return hip_status(launch_lookup_conv(lp, coords, B, H * W, H, W, levels, radius, packed_weight, bias, relu, out,
-                                         (hipStream_t)stream),
+                                         (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_lookup_conv(const float *const *pyr, const float *coords, int B, int H, int W, int levels, int radius,
+                     const void *packed_weight, const float *bias, int relu, float *out, void *stream) {
+    return lookup_conv("corr_lookup_conv", pyr, coords, B, H, W, levels, radius, packed_weight, bias, relu, out,
+                       stream, CORR_PREC_BF16X6);
+}
+
+// include/corr_mi355x_pw_prec.h
+int corr_lookup_conv_prec(const float *const *pyr, const float *coords, int B, int H, int W, int levels, int radius,
+                          const void *packed_weight, const float *bias, int relu, float *out, int precision,
+                          void *stream) {
+    return lookup_conv("corr_lookup_conv_prec", pyr, coords, B, H, W, levels, radius, packed_weight, bias, relu, out,
+                       stream, precision);
 }
 
 int corr_ondemand_lookup_conv(const void *workspace, const float *coords, int B, int D, int H, int W, int levels,
@@ -1023,13 +1041,13 @@ int corr_mask_upsample_pack_weights(const float *w, void *packed, void *stream) 
     return hip_status(launch_mask_upsample_pack(w, packed, (hipStream_t)stream), fn);
 }
 
-int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
-                               const void *packed, const float *bias, float mask_scale, int B, int H, int W,
-                               float *out, void *stream) {
-    static const char *fn = "corr_mask_upsample_forward";
+static int mask_upsample_forward(const char *fn, const float *hidden, int hidden_channels, int hidden_offset,
+                                 const float *flow, const void *packed, const float *bias, float mask_scale, int B,
+                                 int H, int W, float *out, void *stream, int precision) {
     g_err[0] = 0;
-    int rc = check_dims(fn, B, 1, H, W, 1);
-    if (rc) return rc;
+    int rc;
+    if ((rc = check_precision(fn, precision))) return rc;
+    if ((rc = check_dims(fn, B, 1, H, W, 1))) return rc;
     if ((rc = check_window(fn, "hidden_offset", hidden_offset, 256, "hidden_channels", hidden_channels))) return rc;
     if ((rc = check_ptr(fn, hidden, "hidden")) || (rc = check_ptr(fn, flow, "flow")) ||
         (rc = check_ptr(fn, packed, "packed")) || (rc = check_ptr(fn, bias, "bias")) ||
@@ -1043,8 +1061,23 @@ int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hid
         return fail(CORR_EINVAL, "%s: out must not overlap hidden or flow", fn);
     if ((rc = check_packed(fn, packed))) return rc;
     return hip_status(launch_mask_upsample(hidden, hidden_channels, hidden_offset, flow, packed, bias, mask_scale, B,
-                                           H, W, out, (hipStream_t)stream),
+                                           H, W, out, (hipStream_t)stream, precision),
                       fn);
+}
+
+int corr_mask_upsample_forward(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                               const void *packed, const float *bias, float mask_scale, int B, int H, int W,
+                               float *out, void *stream) {
+    return mask_upsample_forward("corr_mask_upsample_forward", hidden, hidden_channels, hidden_offset, flow, packed,
+                                 bias, mask_scale, B, H, W, out, stream, CORR_PREC_BF16X6);
+}
+
+// include/corr_mi355x_pw_prec.h
+int corr_mask_upsample_forward_prec(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
+                                    const void *packed, const float *bias, float mask_scale, int B, int H, int W,
+                                    float *out, int precision, void *stream) {
+    return mask_upsample_forward("corr_mask_upsample_forward_prec", hidden, hidden_channels, hidden_offset, flow,
+                                 packed, bias, mask_scale, B, H, W, out, stream, precision);
 }
 
 size_t corr_flow_enc_weights_bytes(int cout) {

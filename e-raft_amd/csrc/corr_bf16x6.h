@@ -4,8 +4,9 @@
 // corr_ondemand_conv, corr_gru, corr_conv, corr_mask_upsample, corr_enc_front, corr_flow .hip).
 // Internal, not part of the C-ABI.
 //
-// The reduced modes (corr_gru.hip, corr_conv.hip's update-block and encoder forms and
-// corr_enc_front.hip's stem and pointwise kernels, selected per call by the C-ABI's `precision`)
+// The reduced modes (corr_gru.hip, corr_conv.hip's update-block and encoder forms,
+// corr_enc_front.hip's stem and pointwise kernels, corr_lookup_conv.hip's forward and
+// corr_mask_upsample.hip, selected per call by the C-ABI's `precision`)
 // keep fewer of split3's pieces per operand, guards included, and multiply
 // only the products among the kept ones (products<NP>() below):
 //   bf16x6 (NP = 3, the default)  hi, mid, lo   six products:   no narrower than fp32
@@ -89,7 +90,7 @@ __device__ __forceinline__ void six(const u32x4 (&wa)[3], const u32x4 (&xb)[3], 
 
 // The K step of a kernel that keeps NP pieces per operand (wa, xb = the first NP of hi, mid, lo).
 // NP = 3 is six() itself.  The orders of the reduced modes are part of the same contract (pinned
-// by tests/test_precision.py and tests/test_encoder_precision.py):
+// by tests/test_precision.py, tests/test_encoder_precision.py and tests/test_pointwise_precision.py):
 //   NP = 2 (bf16x3):  acs += wm xh;  acs += wh xm;     acc += wh xh      (six()'s order without
 //                     the products that hold a lo piece, and without wm xm)
 //   NP = 1 (bf16):    acc += wh xh                                       (acs is not touched: the

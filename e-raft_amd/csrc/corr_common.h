@@ -198,7 +198,7 @@ size_t lookup_conv_weights_bytes();
 hipError_t launch_lookup_conv_weights(const float *w, int O, int C, void *packed, hipStream_t s);
 hipError_t launch_lookup_conv(const ConstLevelPtrs &pyr, const float *coords, int B, int NQ, int H, int W,
                               int levels, int radius, const void *packed, const float *bias, int relu, float *out,
-                              hipStream_t s);
+                              hipStream_t s, int precision = 0);
 size_t lookup_conv_bwd_workspace(int B, int NQ, int levels);
 hipError_t launch_lookup_conv_bwd(const ConstLevelPtrs &pyr, const float *coords, int B, int NQ, int H, int W,
                                   int levels, int radius, const void *packed, const float *out, int relu,
@@ -284,7 +284,7 @@ size_t mask_upsample_weights_bytes();
 hipError_t launch_mask_upsample_pack(const float *w, void *packed, hipStream_t s);
 hipError_t launch_mask_upsample(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
                                 const void *packed, const float *bias, float mask_scale, int B, int H, int W,
-                                float *out, hipStream_t s);
+                                float *out, hipStream_t s, int precision = 0);
 // The update block's tail (corr_flow.hip): the 7x7 convolution of the flow with the flow's
 // pass-through, and the flow head's 3x3 to 2 channels with the coordinate update.
 bool flow_enc_supported(int cout);

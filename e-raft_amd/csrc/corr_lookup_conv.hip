@@ -20,6 +20,11 @@ namespace {
 // A-fragment order, streamed from L2 one K step ahead) into two accumulators (hi*hi; the rest)
 // and write relu(acc + acs + bias) as [B][O][NQ].  The 324-channel lookup output never reaches
 // HBM.  r = 4, L <= 4, O = 256.
+//
+// `precision` (CORR_PREC_*, forward only) selects the kernel's NP: a reduced mode splits the same
+// looked-up values but stores, fetches and multiplies only the first two pieces (bf16x3, three
+// products) or the first one (bf16, one product, one accumulator) of both operands, from the same
+// pack (corr_bf16x6.h).  The backward kernels run bf16x6 only.
 constexpr int kLcQB = 32, kLcO = 256, kLcKC = 11, kLcKP = 32 * kLcKC /* 352 >= 4*81 */, kLcXS = kLcKP / 2 + 4;
 constexpr int kLcGT = lookup_threads(9, kLcQB), kLcNT = 2 * kLcGT;
 constexpr size_t kLcFwdU = (size_t)(kLcO / 16) * kLcKC * 3 * 64;  // u32x4 of the forward W pack
@@ -40,21 +45,25 @@ __global__ __launch_bounds__(64) void lookup_conv_weights_kernel(const float *__
     store_pieces(dst, h, m, lo);
 }
 
+template <int NP>
 struct LcSmem {
     union {
         LookupSmem<9, kLcQB> lk[2];         // lookups
-        unsigned x[3][kLcQB][kLcXS];        // the tile's pieces [piece][q][k pair] (after the lookups)
+        unsigned x[NP][kLcQB][kLcXS];       // the tile's kept pieces [piece][q][k pair] (after the lookups)
     } u;
     float ct[4 * 81][kLcQB];
 };
 
+// NP: the pieces kept per operand (3 = bf16x6, 2 = bf16x3, 1 = bf16; products<NP>, corr_bf16x6.h).
+// The pack is the same for every NP: a reduced mode skips the 1-KB runs of the pieces it drops.
+template <int NP>
 __global__ __launch_bounds__(kLcNT) void lookup_conv_kernel(ConstLevelPtrs pyr, const float *__restrict__ coords,
                                                              int B, int NQ, int H, int W, int L,
                                                              const u32x4 *__restrict__ frag,
                                                              const float *__restrict__ bias, int relu,
                                                              float *__restrict__ out) {
     constexpr int S = 9, K = S * S, QB = kLcQB;
-    __shared__ LcSmem sm;
+    __shared__ LcSmem<NP> sm;
     const int N = NQ;
     const int nqb = (N + QB - 1) / QB;
     const int b = blockIdx.x / nqb;
@@ -80,8 +89,8 @@ __global__ __launch_bounds__(kLcNT) void lookup_conv_kernel(ConstLevelPtrs pyr, 
         unsigned h, m, lo;
         split3(y0, y1, h, m, lo);
         sm.u.x[0][q][kp] = h;
-        sm.u.x[1][q][kp] = m;
-        sm.u.x[2][q][kp] = lo;
+        if constexpr (NP > 1) sm.u.x[1][q][kp] = m;
+        if constexpr (NP > 2) sm.u.x[2][q][kp] = lo;
     }
     __syncthreads();
     // ---- 256 x 32 x 352 GEMM: wave w < 8 owns output channels [32 w, 32 w + 32) ----
@@ -93,13 +102,13 @@ __global__ __launch_bounds__(kLcNT) void lookup_conv_kernel(ConstLevelPtrs pyr, 
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int c = 0; c < 2; ++c) acc[a][c] = acs[a][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    u32x4 wa[2][2][3];  // [buffer][o-tile][piece]
+    u32x4 wa[2][2][NP];  // [buffer][o-tile][piece]
     auto load_a = [&](int buf, int kc) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const size_t base = (((size_t)(2 * w + t) * kLcKC + kc) * 3) * 64 + lane;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) wa[buf][t][p] = frag[base + 64 * p];
+            for (int p = 0; p < NP; ++p) wa[buf][t][p] = frag[base + 64 * p];
         }
     };
     load_a(0, 0);
@@ -107,16 +116,16 @@ __global__ __launch_bounds__(kLcNT) void lookup_conv_kernel(ConstLevelPtrs pyr, 
     for (int kc = 0; kc < kLcKC; ++kc) {
         const int cur = kc & 1;
         if (kc + 1 < kLcKC) load_a(cur ^ 1, kc + 1);
-        u32x4 xb[2][3];
+        u32x4 xb[2][NP];
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
+            for (int p = 0; p < NP; ++p)
                 xb[c][p] = *reinterpret_cast<const u32x4 *>(&sm.u.x[p][16 * c + fr][16 * kc + fk]);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int c = 0; c < 2; ++c) six(wa[cur][t], xb[c], acc[t][c], acs[t][c]);
+            for (int c = 0; c < 2; ++c) products<NP>(wa[cur][t], xb[c], acc[t][c], acs[t][c]);
     }
     // ---- epilogue: C[row = o][col = q] = acc[4 (lane >> 4) + r][lane & 15] ----
 #pragma unroll
@@ -128,7 +137,7 @@ __global__ __launch_bounds__(kLcNT) void lookup_conv_kernel(ConstLevelPtrs pyr, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int o = 32 * w + 16 * t + 4 * (lane >> 4) + r;
-                float v = split_sum(acc[t][c][r], acs[t][c][r]) + bias[o];
+                float v = (NP == 1 ? acc[t][c][r] : split_sum(acc[t][c][r], acs[t][c][r])) + bias[o];
                 if (relu && v < 0.0f) v = 0.0f;  // torch.relu: a NaN stays a NaN (fmaxf would drop it)
                 __builtin_nontemporal_store(v, &out[((size_t)b * kLcO + o) * N + n]);  // streams past L2
             }
@@ -560,12 +569,25 @@ hipError_t launch_lookup_conv_bwd(const ConstLevelPtrs &pyr, const float *coords
 
 hipError_t launch_lookup_conv(const ConstLevelPtrs &pyr, const float *coords, int B, int NQ, int H, int W,
                               int levels, int radius, const void *packed, const float *bias, int relu, float *out,
-                              hipStream_t s) {
+                              hipStream_t s, int precision) {
     if (radius != 4 || levels < 1 || levels > 4) return hipErrorInvalidValue;  // E-RAFT: r = 4, L <= 4
+    if (!precision_supported(precision)) return hipErrorInvalidValue;
     const u32x4 *frag = static_cast<const u32x4 *>(packed);
     const int nqb = (NQ + kLcQB - 1) / kLcQB;
-    hipLaunchKernelGGL(lookup_conv_kernel, dim3(nqb * B), dim3(kLcNT), 0, s, pyr, coords, B, NQ, H, W, levels, frag,
-                       bias, relu, out);
+    const dim3 grid(nqb * B), block(kLcNT);
+    switch (precision) {
+        case 1:
+            hipLaunchKernelGGL(lookup_conv_kernel<2>, grid, block, 0, s, pyr, coords, B, NQ, H, W, levels, frag, bias,
+                               relu, out);
+            break;
+        case 2:
+            hipLaunchKernelGGL(lookup_conv_kernel<1>, grid, block, 0, s, pyr, coords, B, NQ, H, W, levels, frag, bias,
+                               relu, out);
+            break;
+        default:
+            hipLaunchKernelGGL(lookup_conv_kernel<3>, grid, block, 0, s, pyr, coords, B, NQ, H, W, levels, frag, bias,
+                               relu, out);
+    }
     return hipGetLastError();
 }
 

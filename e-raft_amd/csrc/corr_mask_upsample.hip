@@ -31,6 +31,11 @@
 // no workspace.
 //
 // Non-finite inputs give fp32's pattern (corr_conv.hip's note applies).
+//
+// `precision` (CORR_PREC_*) selects the kernel's NP: the reduced modes stage, fetch and multiply
+// only the first two pieces (bf16x3, three products) or the first one (bf16, one product, one
+// accumulator) of both operands, from the same pack (corr_bf16x6.h).  The softmax, the
+// combination, the flow loads and the stores are the same in every mode.
 #include "corr_bf16x6.h"
 #include "corr_common.h"
 
@@ -76,8 +81,11 @@ struct MaskUpArgs {
     int hc, off, H, W, nxb, tiles, vec;  // nxb blocks per row, tiles = B H nxb, vec: out is 16-B aligned
 };
 
+// NP: the pieces kept per operand (3 = bf16x6, 2 = bf16x3, 1 = bf16; products<NP>, corr_bf16x6.h).
+// The pack is the same for every NP: a reduced mode skips the 1-KB runs of the pieces it drops.
+template <int NP>
 __global__ __launch_bounds__(kMuNT, kMuWaves) void mask_upsample_kernel(MaskUpArgs g) {
-    __shared__ __attribute__((aligned(16))) unsigned xs[3][kMuPX][kMuXS];
+    __shared__ __attribute__((aligned(16))) unsigned xs[NP][kMuPX][kMuXS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = g.H, W = g.W;
@@ -85,12 +93,12 @@ __global__ __launch_bounds__(kMuNT, kMuWaves) void mask_upsample_kernel(MaskUpAr
 
     // ---- A fragments: step s = 9 (K step) + tap of this wave's quarter of the pack ----
     const u32x4 *fq = g.frag + (size_t)q * kMuSteps * 3 * 64 + lane;
-    auto load_a = [&](u32x4 (&wa)[3], int s) {
+    auto load_a = [&](u32x4 (&wa)[NP], int s) {
         s = s < kMuSteps ? s : kMuSteps - 1;  // the last steps re-read the last fragment
 #pragma unroll
-        for (int p = 0; p < 3; ++p) wa[p] = fq[(size_t)(s * 3 + p) * 64];
+        for (int p = 0; p < NP; ++p) wa[p] = fq[(size_t)(s * 3 + p) * 64];
     };
-    u32x4 wa[kMuRing][3];
+    u32x4 wa[kMuRing][NP];
 #pragma unroll
     for (int s = 0; s < kMuAhead; ++s) load_a(wa[s], s);
 
@@ -117,8 +125,8 @@ __global__ __launch_bounds__(kMuNT, kMuWaves) void mask_upsample_kernel(MaskUpAr
             split3(v[i][0], v[i][1], hi, mid, lo);
             const int cp = cp0 + (kMuNT / kMuPX) * i;
             xs[0][px][cp] = hi;
-            xs[1][px][cp] = mid;
-            xs[2][px][cp] = lo;
+            if constexpr (NP > 1) xs[1][px][cp] = mid;
+            if constexpr (NP > 2) xs[2][px][cp] = lo;
         }
     }
     __syncthreads();
@@ -132,17 +140,17 @@ __global__ __launch_bounds__(kMuNT, kMuWaves) void mask_upsample_kernel(MaskUpAr
         for (int p = 0; p < kMuNP; ++p) acc[k][p] = acs[k][p] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int ks = 0; ks < kMuKS; ++ks) {
-        u32x4 xb[kMuNP][3];
+        u32x4 xb[kMuNP][NP];
 #pragma unroll
         for (int p = 0; p < kMuNP; ++p)
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
+            for (int c = 0; c < NP; ++c)
                 xb[p][c] = *reinterpret_cast<const u32x4 *>(&xs[c][16 * p + fr][16 * ks + fk]);
 #pragma unroll
         for (int k = 0; k < kMuTaps; ++k) {
             load_a(wa[(k + kMuAhead) % kMuRing], ks * kMuTaps + k + kMuAhead);
 #pragma unroll
-            for (int p = 0; p < kMuNP; ++p) six(wa[k % kMuRing], xb[p], acc[k][p], acs[k][p]);
+            for (int p = 0; p < kMuNP; ++p) products<NP>(wa[k % kMuRing], xb[p], acc[k][p], acs[k][p]);
         }
     }
 
@@ -183,7 +191,8 @@ __global__ __launch_bounds__(kMuNT, kMuWaves) void mask_upsample_kernel(MaskUpAr
         for (int r = 0; r < 4; ++r) {
             float lg[kMuTaps];
 #pragma unroll
-            for (int k = 0; k < kMuTaps; ++k) lg[k] = g.scale * (bs[k][r] + split_sum(acc[k][p][r], acs[k][p][r]));
+            for (int k = 0; k < kMuTaps; ++k)
+                lg[k] = g.scale * (bs[k][r] + (NP == 1 ? acc[k][p][r] : split_sum(acc[k][p][r], acs[k][p][r])));
             float mx = lg[0];
 #pragma unroll
             for (int k = 1; k < kMuTaps; ++k) mx = fmaxf(mx, lg[k]);
@@ -228,14 +237,20 @@ hipError_t launch_mask_upsample_pack(const float *w, void *packed, hipStream_t s
 
 hipError_t launch_mask_upsample(const float *hidden, int hidden_channels, int hidden_offset, const float *flow,
                                 const void *packed, const float *bias, float mask_scale, int B, int H, int W,
-                                float *out, hipStream_t s) {
+                                float *out, hipStream_t s, int precision) {
+    if (!precision_supported(precision)) return hipErrorInvalidValue;
     MaskUpArgs g{};
     g.hidden = hidden, g.flow = flow, g.bias = bias, g.frag = static_cast<const u32x4 *>(packed), g.out = out;
     g.scale = mask_scale, g.hc = hidden_channels, g.off = hidden_offset, g.H = H, g.W = W;
     g.nxb = (W + 15) / 16;
     g.tiles = B * H * g.nxb;  // <= B H W < 2^31
     g.vec = (uintptr_t)out % 16 == 0;  // (8W floats per output row: every row then is 16-B aligned)
-    hipLaunchKernelGGL(mask_upsample_kernel, dim3((unsigned)((g.tiles + kMuNP - 1) / kMuNP)), dim3(kMuNT), 0, s, g);
+    const dim3 grid((unsigned)((g.tiles + kMuNP - 1) / kMuNP)), block(kMuNT);
+    switch (precision) {
+        case 1: hipLaunchKernelGGL(mask_upsample_kernel<2>, grid, block, 0, s, g); break;
+        case 2: hipLaunchKernelGGL(mask_upsample_kernel<1>, grid, block, 0, s, g); break;
+        default: hipLaunchKernelGGL(mask_upsample_kernel<3>, grid, block, 0, s, g);
+    }
     return hipGetLastError();
 }
 

@@ -49,6 +49,8 @@ TRAIN_EXPORTS = ("corr_upsample_loss_workspace", "corr_upsample_loss", "corr_ups
 ENC_PREC_EXPORTS = ("corr_enc_conv_forward_prec", "corr_enc_stem_forward_prec", "corr_enc_pw_forward_prec")
 # include/corr_mi355x_build_prec.h: the all-pairs build in a precision mode
 BUILD_PREC_EXPORTS = ("corr_build_ex_prec", "corr_build_region_prec")
+# include/corr_mi355x_pw_prec.h: lookup + convc1 and the mask head in a precision mode
+PW_PREC_EXPORTS = ("corr_lookup_conv_prec", "corr_mask_upsample_forward_prec")
 # include/corr_mi355x_train_head.h: the fused loss with the mask head inside the launch
 TRAIN_HEAD_EXPORTS = ("corr_mask_upsample_loss_workspace", "corr_mask_upsample_loss", "corr_mask_upsample_loss_bwd")
 ABI_VERSION = 202  # include/corr_mi355x.h: tiled value pyramid, separable fold, fp32 non-finite rule (bf16x6 bwd)
@@ -196,6 +198,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.corr_enc_pw_forward_prec.argtypes = [vp, i, i, i, i, i, vp, vp, i, vp, vp, sz, i, vp]
     lib.corr_build_ex_prec.argtypes = [i, vp, i, vp, i, i, i, i, i, vp, vp, sz, i, vp]
     lib.corr_build_region_prec.argtypes = [i, vp, i, vp, i, i, i, i, i, i, i, vp, vp, sz, i, i, vp]
+    lib.corr_lookup_conv_prec.argtypes = [vp, vp, i, i, i, i, i, vp, vp, i, vp, i, vp]
+    lib.corr_mask_upsample_forward_prec.argtypes = [vp, i, i, vp, vp, vp, ctypes.c_float, i, i, i, vp, i, vp]
     fl = ctypes.c_float
     lib.corr_upsample_loss_workspace.argtypes, lib.corr_upsample_loss_workspace.restype = [i, i, i], sz
     lib.corr_upsample_loss.argtypes = [vp, vp, vp, vp, i, i, i, i, i, fl, i, vp, vp, sz, vp]
@@ -209,7 +213,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
                                                 sz, vp]
     for f in ("corr_upsample_loss", "corr_upsample_loss_bwd", "corr_sequence_loss", "corr_sequence_loss_bwd",
               "corr_mask_upsample_loss", "corr_mask_upsample_loss_bwd",
-              "corr_gru_half_step_prec", "corr_conv_forward_prec", *ENC_PREC_EXPORTS, *BUILD_PREC_EXPORTS):
+              "corr_gru_half_step_prec", "corr_conv_forward_prec", *ENC_PREC_EXPORTS, *BUILD_PREC_EXPORTS,
+              *PW_PREC_EXPORTS):
         getattr(lib, f).restype = i
     for f in ("corr_ondemand_lookup_conv", "corr_flow_enc_pack_weights", "corr_flow_enc_forward", "corr_flow_head_pack_weights",
               "corr_flow_head_forward", "corr_enc_stem_pack_weights", "corr_enc_stem_forward", "corr_enc_pw_pack_weights", "corr_enc_pw_forward",
@@ -713,15 +718,16 @@ def lookup_conv_weights(weight):
     return packed
 
 
-def lookup_conv(levels, coords, radius, packed, bias, out, relu=True):
-    """corr_lookup_conv: fused lookup + 1x1 conv (+ReLU) -> out [B, 256, H, W]."""
+def lookup_conv(levels, coords, radius, packed, bias, out, relu=True, precision=0):
+    """corr_lookup_conv_prec: fused lookup + 1x1 conv (+ReLU) -> out [B, 256, H, W].  precision is a
+    CORR_PREC_* value (precision.py; 0 = bf16x6 is corr_lookup_conv itself, bit for bit)."""
     B, _, H, W = coords.shape
     pp, c = _ptrs(levels, "pyr"), _dev(coords, "coords")
     _check_levels(levels, B * H * W, H, W, "pyr")
     pw, bs, o = _dev(packed, "packed_weight"), _dev(bias, "bias"), _dev(out, "out")
     with torch.cuda.device(coords.device):
-        _check(load().corr_lookup_conv(pp, c, B, H, W, len(levels), radius, pw, bs, int(bool(relu)), o,
-                                       _stream(coords)))
+        _check(load().corr_lookup_conv_prec(pp, c, B, H, W, len(levels), radius, pw, bs, int(bool(relu)), o,
+                                            int(precision), _stream(coords)))
 
 
 def lookup_conv_bwd(levels, coords, radius, packed, out, relu, grad_out, grad_weight=None, grad_bias=None,
@@ -945,11 +951,12 @@ def mask_upsample_pack_weights(w):
                          "corr_mask_upsample_pack_weights", (), "")
 
 
-def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=None):
-    """corr_mask_upsample_forward: the convex upsampling of flow [B, 2, H, W] by the mask
+def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=None, precision=0):
+    """corr_mask_upsample_forward_prec: the convex upsampling of flow [B, 2, H, W] by the mask
     scale * (W hidden[:, hidden_offset:hidden_offset + 256] + bias), with the pack of
     mask_upsample_pack_weights and bias [576] -> out [B, 2, 8H, 8W] (allocated when None).  The
-    mask itself is never stored.  Returns `out`."""
+    mask itself is never stored.  precision is a CORR_PREC_* value (precision.py; 0 = bf16x6 is
+    corr_mask_upsample_forward itself, bit for bit).  Returns `out`."""
     hp = _dev(hidden, "hidden")
     if hidden.dim() != 4:
         raise ValueError(f"hidden must be [B, C, H, W] (got {tuple(hidden.shape)})")
@@ -972,8 +979,8 @@ def mask_upsample_forward(hidden, hidden_offset, flow, packed, bias, scale, out=
     if tuple(out.shape) != (B, 2, 8 * H, 8 * W) or out.device != hidden.device:
         raise ValueError(f"out must be [{B}, 2, {8 * H}, {8 * W}] on {hidden.device} (got {tuple(out.shape)})")
     with torch.cuda.device(hidden.device):
-        _check(lib.corr_mask_upsample_forward(hp, hc, hidden_offset, fp, pk, bp, float(scale), B, H, W, op,
-                                              _stream(hidden)))
+        _check(lib.corr_mask_upsample_forward_prec(hp, hc, hidden_offset, fp, pk, bp, float(scale), B, H, W, op,
+                                                   int(precision), _stream(hidden)))
     return out
 
 

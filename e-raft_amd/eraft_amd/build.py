@@ -24,6 +24,7 @@ SOURCES = ["corr_build.hip", "corr_build_split.hip", "corr_build_bf16.hip", "cor
 # every header counts as a dependency of every translation unit (paths relative to csrc/)
 HEADERS = sorted(glob.glob("*.h", root_dir=SRC)) + [os.path.join("..", "..", "include", h)
                                                     for h in ("corr_mi355x.h", "corr_mi355x_build_prec.h", "corr_mi355x_enc_prec.h",
+                                                              "corr_mi355x_pw_prec.h",
                                                               "corr_mi355x_train.h", "corr_mi355x_train_head.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

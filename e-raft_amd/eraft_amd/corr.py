@@ -387,11 +387,15 @@ class CorrBlock:
         _lib.lookup(self._state.levels, coords, self.radius, out)
         return out
 
-    def lookup_conv(self, coords, weight, bias, relu=True):
+    def lookup_conv(self, coords, weight, bias, relu=True, precision=None):
         """Lookup fused with the motion encoder's first layer, relu(convc1(self(coords)))
         (update.py:68,75), without materialising the lookup output.  weight: convc1.weight
         [256, L*K, 1, 1]; bias [256].  Under autograd (training) gradients reach the weight,
-        the bias and, through the build's backward, both feature maps (_LookupConvFn)."""
+        the bias and, through the build's backward, both feature maps (_LookupConvFn).
+        precision: the convolution's mode, "bf16x6", "bf16x3" or "bf16" (precision.py; the looked-up
+        values are the same in every mode); None reads ERAFT_AMD_POINTWISE_PRECISION, else "bf16x6".
+        A call recorded for autograd runs "bf16x6", whatever is asked."""
+        mode = _precision.code(_precision.resolve_pointwise(None) if precision is None else precision)
         self._check_coords(coords)
         B, _, H, W = coords.shape
         K = (2 * self.radius + 1) ** 2
@@ -409,7 +413,7 @@ class CorrBlock:
         packed = _weight_pack(weight)  # split once per weight version (every GRU iteration reuses it)
         out = torch.empty((B, weight.shape[0], H, W), dtype=torch.float32, device=coords.device)
         _lib.lookup_conv(self._state.levels, coords, self.radius, packed,
-                         bias.detach().contiguous().float(), out, relu)
+                         bias.detach().contiguous().float(), out, relu, precision=mode)
         return out
 
     @staticmethod

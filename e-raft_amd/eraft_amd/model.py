@@ -21,7 +21,8 @@ import torch.nn.functional as F
 from .corr import CorrBlock
 from .ondemand import OnDemandConvCorrBlock, OnDemandCorrBlock
 from .precision import (DEFAULT as _PRECISION, resolve as _resolve_precision, resolve_corr as _resolve_corr_precision,
-                        resolve_encoder as _resolve_encoder_precision)
+                        resolve_encoder as _resolve_encoder_precision,
+                        resolve_pointwise as _resolve_pointwise_precision)
 from .utils import coords_grid
 
 
@@ -366,11 +367,13 @@ class ERAFT(nn.Module):
     # mask is neither stored nor saved for backward.  Default off (DESIGN §32 has the measurements).
     fuse_mask_loss = os.environ.get("ERAFT_AMD_FUSE_MASK_LOSS", "0") == "1"
     # The precision mode of the GRU and the update block's 3x3 convolutions ("bf16x6", "bf16x3" or
-    # "bf16": precision.py), that of the two encoders' convolutions and that of the correlation
-    # build; an instance takes each from its config (below).
+    # "bf16": precision.py), that of the two encoders' convolutions, that of the correlation
+    # build and that of the two fused 1x1 convolutions (lookup + convc1, the mask head); an
+    # instance takes each from its config (below).
     precision = _PRECISION
     encoder_precision = _PRECISION
     corr_precision = _PRECISION
+    pointwise_precision = _PRECISION
 
     def __init__(self, config, n_first_channels):
         super().__init__()
@@ -391,17 +394,21 @@ class ERAFT(nn.Module):
                                  n_first_channels=n_first_channels)
         self.update_block = BasicUpdateBlock(self.corr_levels, self.corr_radius, hidden_dim=hdim)
         # The reference's switch (model/eraft.py:102-133 puts fnet, cnet and the update block under
-        # one autocast) is two knobs here, and setting both corresponds to it:
+        # one autocast) is three knobs here, and setting all three corresponds to it:
         #   `mixed_precision` (absent / False: "bf16x6", every product exact as before; True:
         #   "bf16x3"; or a mode's name), overridden by ERAFT_AMD_PRECISION=<name>, reaches the GRU's
         #   eight convolutions and the update block's convc2, convf2, conv and the two heads' first
         #   convolutions, where their fused kernels run (ERAFT_AMD_FUSE_GRU=1 / ERAFT_AMD_FUSE_UPDATE=1);
         #   `encoder_precision` (the same values), overridden by ERAFT_AMD_ENCODER_PRECISION=<name>,
         #   reaches the 16 convolutions of fnet and the 16 of cnet (stem, 3x3 stages, 1x1 projections
-        #   and head), where encoder.encoder_forward runs (ERAFT_AMD_FUSE_ENCODER=1).
-        # Both act at inference only; the torch paths and training stay fp32.  convf1, the flow
-        # head's second convolution, the mask head and the lookup with convc1 stay "bf16x6".
-        # A third knob is the correlation build's own:
+        #   and head), where encoder.encoder_forward runs (ERAFT_AMD_FUSE_ENCODER=1);
+        #   `pointwise_precision` (the same values), overridden by ERAFT_AMD_POINTWISE_PRECISION=<name>,
+        #   reaches convc1 inside CorrBlock.lookup_conv (ERAFT_AMD_FUSE_CONV) and the mask head's 1x1
+        #   convolution inside upsample.mask_upsample (ERAFT_AMD_FUSE_UPSAMPLE=1); `mixed_precision`
+        #   does not set it, and the on-demand blocks never get it.
+        # All act at inference only; the torch paths and training stay fp32.  convf1 and the flow
+        # head's second convolution stay "bf16x6": the flow enters and leaves through them.
+        # A fourth knob is the correlation build's own:
         #   `corr_precision` (the same values), overridden by ERAFT_AMD_CORR_PRECISION=<name>, reaches
         #   CorrBlock's all-pairs build (the lookups read whatever values it left in the pyramid).
         # The reference casts the feature maps to fp32 before its CorrBlock, outside the autocast, so
@@ -413,6 +420,7 @@ class ERAFT(nn.Module):
         self.encoder_precision = _resolve_encoder_precision(config)
         self.fnet.precision = self.cnet.precision = self.encoder_precision
         self.corr_precision = _resolve_corr_precision(config)
+        self.pointwise_precision = _resolve_pointwise_precision(config)
 
     def freeze_bn(self):
         for m in self.modules():
@@ -481,11 +489,14 @@ class ERAFT(nn.Module):
         # made once per forward and its flow head's kernel also does the coordinate update: the loop
         # then issues no coords1 + delta and no coords1 - coords0 (flow is the kernel's flow_out)
         ub, ws, flow = self.update_block, None, None
+        # (the default mode is passed by omission, as the build's; the on-demand blocks have no modes)
+        pw_mask = {} if self.pointwise_precision == _PRECISION else {"precision": self.pointwise_precision}
+        pw = {} if self.alternate_corr else pw_mask
         for it in range(iters):
             coords1 = coords1.detach()
             if fuse:
                 enc = ub.encoder
-                corr = corr_fn.lookup_conv(coords1, enc.convc1.weight, enc.convc1.bias)
+                corr = corr_fn.lookup_conv(coords1, enc.convc1.weight, enc.convc1.bias, **pw)
             else:
                 corr = corr_fn(coords1)
             if flow is None:
@@ -516,7 +527,7 @@ class ERAFT(nn.Module):
                 net, hidden, delta, *upd = ub(net, inp, corr, flow, fuse, defer_mask=True, **kw)
                 coords1, flow = upd if tail else (coords1 + delta, None)
                 hidden, off = channel_window(hidden)
-                up = mask_upsample(ub.mask[2], hidden, off, flow if tail else coords1 - coords0)
+                up = mask_upsample(ub.mask[2], hidden, off, flow if tail else coords1 - coords0, **pw_mask)
             else:
                 net, up_mask, delta, *upd = ub(net, inp, corr, flow, fuse, **kw)
                 coords1, flow = upd if tail else (coords1 + delta, None)

@@ -8,7 +8,7 @@ A mode names the pieces of the exact three-piece bf16 split that a kernel keeps 
   "bf16x3"  hi, mid: three products, operands to 2^-18 and the dropped mid x mid to 2^-16 relative
   "bf16"    hi: one product, operands to 2^-9 relative
 
-Accumulation is fp32 in every mode.  Three knobs choose a mode, each for its own layers:
+Accumulation is fp32 in every mode.  Four knobs choose a mode, each for its own layers:
 
   `mixed_precision` / ERAFT_AMD_PRECISION (resolve)
       the fused GRU half steps (the eight convolutions of SepConvGRU) and the update block's fused
@@ -26,10 +26,19 @@ Accumulation is fp32 in every mode.  Three knobs choose a mode, each for its own
       only its own key and variable do.  A build recorded for autograd runs "bf16x6"; the
       on-demand blocks (no all-pairs volume) use the fp32 MFMA and ignore it.
 
-The reference's single switch wraps the encoders and the update block in one autocast, so it
-corresponds to setting the first two.  The torch paths and training stay fp32 and ignore all
-three; convf1, the flow head's second convolution, the mask head with the upsampling and the
-lookup with convc1 stay "bf16x6" under any of them (the lookups read whatever values the build
+  `pointwise_precision` / ERAFT_AMD_POINTWISE_PRECISION (resolve_pointwise)
+      the two 1x1 convolutions of the update loop that are fused with their neighbours: convc1
+      inside CorrBlock.lookup_conv (ERAFT_AMD_FUSE_CONV, on by default; the looked-up values are
+      the same in every mode, only the product after them changes) and the mask head's second
+      convolution inside upsample.mask_upsample (ERAFT_AMD_FUSE_UPSAMPLE=1), at inference.  A
+      lookup_conv recorded for autograd runs "bf16x6"; the on-demand blocks ignore it.
+      `mixed_precision` does NOT set it: it keeps the reach it had.
+
+The reference's single switch wraps the encoders and the update block in one autocast
+(model/eraft.py:102-133, model/update.py:68,75,99-107), so it corresponds to setting the first two
+and the fourth.  The torch paths and training stay fp32 and ignore all four; convf1 and the flow
+head's second convolution stay "bf16x6" under any of them (the flow enters and leaves through
+them), as does the on-demand lookup fused with convc1 (the lookups read whatever values the build
 left in the pyramid).
 """
 from __future__ import annotations
@@ -42,6 +51,7 @@ DEFAULT = "bf16x6"
 ENV = "ERAFT_AMD_PRECISION"
 ENCODER_ENV = "ERAFT_AMD_ENCODER_PRECISION"
 CORR_ENV = "ERAFT_AMD_CORR_PRECISION"
+POINTWISE_ENV = "ERAFT_AMD_POINTWISE_PRECISION"
 
 
 def code(name) -> int:
@@ -88,3 +98,11 @@ def resolve_corr(config=None) -> str:
     ERAFT_AMD_CORR_PRECISION=<name>; a variable that is set but empty counts as unset, any other
     unknown name raises.  Independent of `mixed_precision` and `encoder_precision`."""
     return _resolve(config, "corr_precision", CORR_ENV)
+
+
+def resolve_pointwise(config=None) -> str:
+    """The mode name of a model's lookup + convc1 and mask head launches: the config key
+    `pointwise_precision` (absent, None or False: "bf16x6"; True: "bf16x3"; a string: that mode),
+    overridden by ERAFT_AMD_POINTWISE_PRECISION=<name>; a variable that is set but empty counts as
+    unset, any other unknown name raises.  Independent of the other three knobs."""
+    return _resolve(config, "pointwise_precision", POINTWISE_ENV)

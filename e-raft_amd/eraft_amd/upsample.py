@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, precision as _precision
 from ._cache import cached
 
 def _mask_pack(conv):
@@ -35,10 +35,13 @@ def channel_window(t):
     return t.contiguous(), 0
 
 
-def mask_upsample(conv, hidden, hidden_offset, flow, scale=0.25):
+def mask_upsample(conv, hidden, hidden_offset, flow, scale=0.25, precision="bf16x6"):
     """ERAFT.upsample_flow(flow, scale * conv(hidden[:, hidden_offset:hidden_offset + 256])) for the
     1x1 Conv2d `conv` (256 -> 576, with bias): hidden [B, C, H, W] (read in place), flow
-    [B, 2, H, W]; fp32 on the GPU.  Returns the prediction [B, 2, 8H, 8W]."""
+    [B, 2, H, W]; fp32 on the GPU.  precision: the convolution's mode, "bf16x6", "bf16x3" or "bf16"
+    (precision.py; the softmax and the combination are fp32 in every mode).  Returns the prediction
+    [B, 2, 8H, 8W]."""
+    mode = _precision.code(precision)
     for t, nm in ((hidden, "hidden"), (flow, "flow")):
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
             raise RuntimeError(f"{nm} must be a tensor on an MI355X (HIP) device: eraft_amd has no CPU fallback")
@@ -46,4 +49,5 @@ def mask_upsample(conv, hidden, hidden_offset, flow, scale=0.25):
         raise ValueError(f"mask_upsample needs a 256 -> 576 1x1 convolution with a bias "
                          f"(got weight {tuple(conv.weight.shape)})")
     packed, bias = _mask_pack(conv)
-    return _lib.mask_upsample_forward(hidden.detach(), hidden_offset, flow.detach().contiguous(), packed, bias, scale)
+    return _lib.mask_upsample_forward(hidden.detach(), hidden_offset, flow.detach().contiguous(), packed, bias, scale,
+                                      precision=mode)
